@@ -12,7 +12,11 @@ Multi-GPU (torch.distributed.run, one rank per GPU): agents shard with no
 data-path collective (weak scaling: --agents per GPU); a barrier + device sync
 brackets the timed region and the slowest rank's time is reported.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+steps and prints the line; --full adds what the headline figure does not need
+(the per-kernel roofline, the status / certified-path counts, the CPU baseline;
+null in a plain run's line).  --dump-outputs DIR writes a fixed sample of the
+last timed step's outputs as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -177,7 +181,64 @@ def parse():
                          "= the engine's default (1 in the reference's mode, 0 with demand charges)")
     ap.add_argument("--pmc-dir", default=os.path.join(REPO, "profiles", "pmc"),
                     help="per-workload PMC summaries (traffic field); none -> traffic null")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: the per-kernel roofline, the "
+                         "status / certified-path counts and the CPU baseline (a plain run leaves them null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a fixed, seeded sample of the last step's outputs "
+                         "(caller order) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+# --dump-outputs: agents sampled per output class (a prefix of one seeded
+# permutation each, so the classes nest): 18 scalars x 32768 x 8 B = 4.7 MB,
+# 7 yearly arrays x 4096 x 51 x 8 B = 11.7 MB, 3 hourly planes x 256 x 8760 x
+# 4 B = 26.9 MB (twice that for f64 planes): under 64 MB in all
+DUMP_SEED = 20260019
+DUMP_SCALAR, DUMP_YEARLY, DUMP_HOURLY = 32768, 4096, 256
+
+
+def dump_agents(n: int) -> np.ndarray:
+    """Caller-order indices of the dumped agents, the same for every run of n
+    agents; the yearly / hourly samples are its first DUMP_YEARLY / DUMP_HOURLY."""
+    return np.random.default_rng(DUMP_SEED).permutation(n)[:DUMP_SCALAR].astype(np.int64)
+
+
+def dump_outputs(path: str, out, perm) -> None:
+    """What size() left in `out` for the sampled agents, as the caller receives
+    it (engine.outputs_to_host's layout: caller order, [agent][year] yearly
+    arrays, [agent][hour] hourly planes), one DIR/<name>.npy per output plus
+    agent_index.npy; integers as float64, the rest in their own precision."""
+    import torch
+    from dgen_amd import _lib
+    os.makedirs(path, exist_ok=True)
+    n = out["status"].numel()
+    idx = dump_agents(n)
+    rows = idx
+    if perm is not None:                      # device row of caller agent perm[j] is j
+        inv = np.empty(n, np.int64)
+        inv[np.asarray(perm, np.int64)] = np.arange(n, dtype=np.int64)
+        rows = inv[idx]
+    rows = torch.as_tensor(rows, device=out["status"].device)
+    total = 0
+
+    def put(name, a):
+        nonlocal total
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+    put("agent_index", idx)
+    for name, _ in _lib.OUTPUT_SCALARS:
+        put(name, out[name].index_select(0, rows).cpu().numpy())
+    for name in _lib.OUTPUT_YEARLY:
+        put(name, out[name].index_select(0, rows[:DUMP_YEARLY]).cpu().numpy())
+    for name in _lib.OUTPUT_HOURLY:
+        t = out.get(name)
+        if t is not None:                     # hour-quad tiles [NH / 4][n][4] -> [agent][hour]
+            h = t.index_select(1, rows[:DUMP_HOURLY]).permute(1, 0, 2)
+            put(name, h.reshape(h.shape[0], -1).cpu().numpy())
+    assert total <= 64 << 20, total
 
 
 def _lib_default_split() -> int:
@@ -291,90 +352,17 @@ def timed_region(step, steps: int, sync, dist_mod=None, device=None) -> float:
     return el
 
 
-def main():
-    args = parse()
-    # --gpus N without torch.distributed.run: start N rank children before any
-    # GPU call (dgen_amd.launch); under torchrun, WORLD_SIZE must equal --gpus
-    from dgen_amd.launch import maybe_launch
-    st = maybe_launch(args.gpus, __file__, sys.argv[1:])
-    if st is not None:
-        sys.exit(st)
-    ws, rank, local = dist_env()
-    import torch
-    import torch.distributed as dist
-    # one rank per GPU (RCCL); DGEN_DIST_BACKEND=gloo rehearses the N > 1 flow
-    # with several ranks on one GPU (device = LOCAL_RANK mod the visible GPUs)
-    backend = os.environ.get("DGEN_DIST_BACKEND", "nccl")
-    if ws > 1:
-        local = local % max(1, torch.cuda.device_count())
-        torch.cuda.set_device(local)
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend)
-    from dgen_amd.config import EngineConfig
-    from dgen_amd.engine import Engine, profile_order
-    from dgen_amd.synth import make_population
-
-    if args.hb_nem is not None:
-        os.environ["DGEN_HB_NEM"] = str(args.hb_nem)              # read by dgen_open
-    if args.hb_split is not None:
-        os.environ["DGEN_HB_SPLIT"] = str(args.hb_split)          # read by dgen_open
-    pop = make_population(args.config, args.agents, seed=20260000 + 3 + 7919 * rank)
-    # demand-charge configs run the extension mode; every other config the
-    # reference's switch (SKIP_DEMAND_CHARGES = True, ff:35)
-    eng = Engine(local if ws > 1 else 0, EngineConfig(skip_demand_charges=pop.skip_demand_charges,
-                                                      batt_update_hours=args.replan_hours,
-                                                      exact_brent=args.exact))
-    if args.chunks is not None:
-        eng.set_pipeline(args.chunks)
-    if args.hb_months is not None:
-        eng.set_hourly_segment(args.hb_months)
-    if args.no_batt:
-        eng.set_battery(False)
-    eng.load_profiles(pop.shapes, pop.cfs, pop.wholesale)
-    eng.set_tariffs(pop.tariffs, pop.demand)
-    eng.set_switches(pop.switches)
-    order = None if args.caller_order else profile_order(pop.cols, args.order_major)
-    batch = eng.upload_agents(pop.cols, pop.n_scratch, order=order)
-    out = eng.alloc_outputs(batch.n, hourly=not args.no_hourly)
-    c_out = eng.c_outputs(out)
-    torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        eng.size(batch, out, c_out)
-    torch.cuda.synchronize()
-    eng.kernel_times()                      # drop warmup events
-
-    el = timed_region(lambda: eng.size(batch, out, c_out), args.steps, torch.cuda.synchronize,
-                      dist if ws > 1 else None, eng.dev if backend == "nccl" else "cpu")
-    ms_size, ms_hourly, ms_fin, cnt = eng.kernel_times()
-    if os.environ.get("DGEN_PHASE_PROF") and hasattr(eng.lib, "dgen_phase_read"):   # ablation builds only
-        import ctypes
-        ph = (ctypes.c_uint64 * 16)()
-        if eng.lib.dgen_phase_read(ph, 0) == 0:
-            print(json.dumps({"phase_cycles": list(ph)}), file=sys.stderr, flush=True)
-    if hasattr(eng.lib, "dgen_clk_read"):      # clock-stamp ablation builds only (scripts/make_ablations.py)
-        import ctypes
-        import numpy as _np
-        ck = (ctypes.c_uint64 * (4 * 8192))()
-        if eng.lib.dgen_clk_read(ck) == 0:
-            a = _np.frombuffer(ck, dtype=_np.uint64).reshape(4, 8192).astype(_np.float64)
-            ok = (a[3] > a[1]) & (a[2] > a[0])
-            ghz = (a[2][ok] - a[0][ok]) / (a[3][ok] - a[1][ok]) * 0.1
-            if ghz.size:
-                print(json.dumps({"hourly_clock_ghz": {"median": float(_np.median(ghz)), "p10": float(_np.percentile(ghz, 10)),
-                                                       "p90": float(_np.percentile(ghz, 90)), "blocks": int(ghz.size)}}),
-                      file=sys.stderr, flush=True)
-
+def full_report(args, pop, eng, batch, out, kms_cnt):
+    """--full: the counts and the roofline a plain run leaves out, from the
+    last timed call's outputs and the HIP-event kernel times `kms_cnt`
+    (Engine.kernel_times()): (agents with status errors, exact re-runs per
+    step, roofline)."""
+    ms_size, ms_hourly, ms_fin, cnt = kms_cnt
     st = out["status"].cpu().numpy()
     n_bad = int(((st & 0x3B) != 0).sum())
     # agents the last timed call re-ran in the oracle's arithmetic (certified
     # Brent paths, dgen_set_exact; their cost is inside k_size's time)
     n_exact = eng.exact_count()
-    total_agents = args.agents * ws * args.steps
-    value = total_agents / el
-
     # which scratch-slot agents moved the f64 system-output plane and which a
     # compact record (the battery case's final tariff, the batch's switches)
     dcols = pop.cols if batch.perm is None else {k: np.asarray(v)[batch.perm] for k, v in pop.cols.items()}
@@ -437,9 +425,96 @@ def main():
                      else (f"{dom} is fp64-VALU / latency bound (the year lanes re-bill per evaluation): "
                            "bound/frac are its PMC VALU-busy share; hbm_frac is secondary") if valu_bound
                      else f"{dom}: no PMC summary for this workload, HBM fraction only")}
+    return n_bad, n_exact, roof
+
+
+def main():
+    args = parse()
+    # --gpus N without torch.distributed.run: start N rank children before any
+    # GPU call (dgen_amd.launch); under torchrun, WORLD_SIZE must equal --gpus
+    from dgen_amd.launch import maybe_launch
+    st = maybe_launch(args.gpus, __file__, sys.argv[1:])
+    if st is not None:
+        sys.exit(st)
+    ws, rank, local = dist_env()
+    import torch
+    import torch.distributed as dist
+    # one rank per GPU (RCCL); DGEN_DIST_BACKEND=gloo rehearses the N > 1 flow
+    # with several ranks on one GPU (device = LOCAL_RANK mod the visible GPUs)
+    backend = os.environ.get("DGEN_DIST_BACKEND", "nccl")
+    if ws > 1:
+        local = local % max(1, torch.cuda.device_count())
+        torch.cuda.set_device(local)
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        else:
+            dist.init_process_group(backend)
+    from dgen_amd.config import EngineConfig
+    from dgen_amd.engine import Engine, profile_order
+    from dgen_amd.synth import make_population
+
+    if args.hb_nem is not None:
+        os.environ["DGEN_HB_NEM"] = str(args.hb_nem)              # read by dgen_open
+    if args.hb_split is not None:
+        os.environ["DGEN_HB_SPLIT"] = str(args.hb_split)          # read by dgen_open
+    pop = make_population(args.config, args.agents, seed=20260000 + 3 + 7919 * rank)
+    # demand-charge configs run the extension mode; every other config the
+    # reference's switch (SKIP_DEMAND_CHARGES = True, ff:35)
+    eng = Engine(local if ws > 1 else 0, EngineConfig(skip_demand_charges=pop.skip_demand_charges,
+                                                      batt_update_hours=args.replan_hours,
+                                                      exact_brent=args.exact))
+    if args.chunks is not None:
+        eng.set_pipeline(args.chunks)
+    if args.hb_months is not None:
+        eng.set_hourly_segment(args.hb_months)
+    if args.no_batt:
+        eng.set_battery(False)
+    eng.load_profiles(pop.shapes, pop.cfs, pop.wholesale)
+    eng.set_tariffs(pop.tariffs, pop.demand)
+    eng.set_switches(pop.switches)
+    order = None if args.caller_order else profile_order(pop.cols, args.order_major)
+    batch = eng.upload_agents(pop.cols, pop.n_scratch, order=order)
+    out = eng.alloc_outputs(batch.n, hourly=not args.no_hourly)
+    c_out = eng.c_outputs(out)
+    torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        eng.size(batch, out, c_out)
+    torch.cuda.synchronize()
+    eng.kernel_times()                      # drop warmup events
+
+    el = timed_region(lambda: eng.size(batch, out, c_out), args.steps, torch.cuda.synchronize,
+                      dist if ws > 1 else None, eng.dev if backend == "nccl" else "cpu")
+    kms_cnt = eng.kernel_times()
+    if os.environ.get("DGEN_PHASE_PROF") and hasattr(eng.lib, "dgen_phase_read"):   # ablation builds only
+        import ctypes
+        ph = (ctypes.c_uint64 * 16)()
+        if eng.lib.dgen_phase_read(ph, 0) == 0:
+            print(json.dumps({"phase_cycles": list(ph)}), file=sys.stderr, flush=True)
+    if hasattr(eng.lib, "dgen_clk_read"):      # clock-stamp ablation builds only (scripts/make_ablations.py)
+        import ctypes
+        import numpy as _np
+        ck = (ctypes.c_uint64 * (4 * 8192))()
+        if eng.lib.dgen_clk_read(ck) == 0:
+            a = _np.frombuffer(ck, dtype=_np.uint64).reshape(4, 8192).astype(_np.float64)
+            ok = (a[3] > a[1]) & (a[2] > a[0])
+            ghz = (a[2][ok] - a[0][ok]) / (a[3][ok] - a[1][ok]) * 0.1
+            if ghz.size:
+                print(json.dumps({"hourly_clock_ghz": {"median": float(_np.median(ghz)), "p10": float(_np.percentile(ghz, 10)),
+                                                       "p90": float(_np.percentile(ghz, 90)), "blocks": int(ghz.size)}}),
+                      file=sys.stderr, flush=True)
+
+    total_agents = args.agents * ws * args.steps
+    value = total_agents / el
+    if args.dump_outputs and rank == 0:       # rank 0's shard, before anything else touches `out`
+        dump_outputs(args.dump_outputs, out, batch.perm)
+
+    n_bad = n_exact = roof = None
+    if args.full:
+        n_bad, n_exact, roof = full_report(args, pop, eng, batch, out, kms_cnt)
 
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu:
         try:
             cpu = cpu_baseline(pop, args.cpu_seconds, args.cpu_threads, args.replan_hours)
         except Exception as e:  # the baseline never blocks the GPU number

@@ -8,7 +8,7 @@
 #   smoke      __graft_entry__.smoke()
 #   bench      one bench line per BENCH ("config:agents[:extra,args]" ..., the
 #              extra bench.py arguments comma-separated; default the driver's
-#              own no-flag run)
+#              own run with --full)
 #   ab         one bench line per ';'-separated VARIANTS entry
 #              ("[lib=<name>] <bench.py args>"; lib= picks ablate/libdgen_<name>.so,
 #              built by scripts/make_ablations.py)
@@ -39,7 +39,7 @@ stop() {
 line() { grep '^{' "$1" | tail -1 | python3 -c "
 import json, sys
 for l in sys.stdin:
-    d = json.loads(l); r = d.get('roofline', {})
+    d = json.loads(l); r = d.get('roofline') or {}
     km = {k: round(v, 2) for k, v in r.get('kernel_ms', {}).items() if isinstance(v, float)}
     print(f\"   value={d['value']:.4g} {d['unit']} ms/step={d['ms_per_step']:.2f} kern={km} \"
           f\"bound={r.get('bound')} frac={r.get('frac')}\")" 2>/dev/null || tail -2 "$1"; }
@@ -60,15 +60,15 @@ for step in "$@"; do
     echo "smoke rc=$rc"; tail -2 $O/smoke.log; stop $rc;;
   bench)
     for b in ${BENCH:-default}; do
-      if [ "$b" = default ]; then args=""; name=default
+      if [ "$b" = default ]; then args="--full"; name=default
       else IFS=: read -r cfg ag extra <<< "$b"; extra=${extra//,/ }
-           args="--config $cfg --agents $ag ${extra:---steps 5 --warmup 1 --no-cpu}"
+           args="--config $cfg --agents $ag ${extra:---steps 5 --warmup 1 --full --no-cpu}"
            name=${cfg}_$ag${BENCH_SUFFIX:-}; [ -n "$extra" ] && name=${name}_$(echo "$extra" | tr -dc 'a-z0-9' | cut -c1-24); fi
       timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py $args > $O/bench_$name.log 2> $O/bench_$name.err; rc=$?
       echo "bench $name rc=$rc"; line $O/bench_$name.log; stop $rc
     done;;
   ab)
-    IFS=';' read -ra VARS <<< "${VARIANTS:---no-cpu}"
+    IFS=';' read -ra VARS <<< "${VARIANTS:---full --no-cpu}"
     k=0
     for v in "${VARS[@]}"; do
       k=$((k+1)); lib=""; args="$v"
@@ -83,7 +83,7 @@ for step in "$@"; do
     for wa in $PROF; do
       W=${wa%%:*}; A=${wa##*:}
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$W -o run -- \
-        python3 $R/bench.py --config $W --agents $A --steps 5 --warmup 1 --no-cpu > $O/trace_$W.log 2>&1); rc=$?
+        python3 $R/bench.py --config $W --agents $A --steps 5 --warmup 1 --full --no-cpu > $O/trace_$W.log 2>&1); rc=$?
       echo "trace $W rc=$rc"; line $O/trace_$W.log; stop $rc
     done;;
   pmc)
@@ -108,7 +108,7 @@ for step in "$@"; do
     fi;;
   rehearse)
     DGEN_DIST_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 ${REH_BENCH_ARGS:---agents 200000 --steps 5 --warmup 1} \
+      --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 ${REH_BENCH_ARGS:---agents 200000 --steps 5 --warmup 1 --full} \
       > $O/bench_n2_gloo.log 2>&1; rc=$?
     echo "bench n2 gloo rc=$rc"; line $O/bench_n2_gloo.log; stop $rc
     DGEN_DIST_BACKEND=gloo timeout -k 10 700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
