@@ -100,6 +100,16 @@ class Outputs(ctypes.Structure):
                 + [("hourly_f64", ctypes.c_int32), ("pad_", ctypes.c_int32)])
 
 
+DIGEST_F64 = ["import_kwh", "export_kwh", "peak_import_kw", "peak_export_kw"]
+DIGEST_I32 = ["peak_import_hour", "peak_export_hour"]
+DIGEST_FIELDS = DIGEST_F64 + DIGEST_I32
+
+
+class DigestOut(ctypes.Structure):
+    """dgen_digest_out: [12][n] month-major device planes, any may be NULL."""
+    _fields_ = [(name, _vp) for name in DIGEST_FIELDS]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -117,6 +127,7 @@ EXPORTED = [
     "dgen_kernel_times", "dgen_last_paths", "dgen_set_dc_prebuild", "dgen_segment_sums", "dgen_max_market_share", "dgen_diffusion",
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
+    "dgen_plane_digest",
 ]
 
 
@@ -194,6 +205,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_segment_sums.argtypes = [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _vp]
     L.dgen_rows_seq_sum.restype = _i32
     L.dgen_rows_seq_sum.argtypes = [_vp, _vp, _i64, _vp, _i64, _vp, _vp]
+    L.dgen_plane_digest.restype = _i32
+    L.dgen_plane_digest.argtypes = [_vp, _vp, _i32, _i64, ctypes.POINTER(DigestOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

@@ -5069,6 +5069,68 @@ __global__ void k_finance_series(Series6 src, const int32_t* __restrict__ len, i
     out[t] = isfinite(v) ? v : 0.0;
 }
 
+// ---------------------------------------------------------------------------
+// Per-agent monthly grid-exchange digest of one hourly plane (dgen_plane_digest;
+// the definition is in include/dgen_hip.h).  Lane per (agent, month): grid
+// (ceil(n / 256), 12), lane = agent, so a wave loads 64 consecutive agents'
+// 16-B hour quads (1 KB contiguous at fp32, 2 KB at fp64).  A month is a whole
+// number of days (c_month_start_day) and a day six quads: the lane issues a
+// day's six loads together, then folds its 24 hours in hour order into six
+// scalars.  No LDS, no atomics, no cross-lane traffic.
+// The sums add 0.0 for an hour of the other sign (or NaN): x + 0.0 == x for
+// every x >= 0, so each sum is the sequential fp64 sum of its own hours.
+// ---------------------------------------------------------------------------
+constexpr int DG_BLOCK = 256;
+template <typename V>
+__global__ void __launch_bounds__(DG_BLOCK)
+k_plane_digest(const V* __restrict__ plane, int64_t n, dgen_digest_out out) {
+    const int64_t i = (int64_t)blockIdx.x * DG_BLOCK + threadIdx.x;
+    const int m = blockIdx.y;
+    if (i >= n || m >= 12) return;
+    const int d0 = c_month_start_day[m], d1 = c_month_start_day[m + 1];
+    const int64_t qs = n * 4;                     // elements from an agent's quad to its next
+    const V* p = plane + ((int64_t)d0 * 6 * n + i) * 4;
+    double imp = 0.0, ex = 0.0, pk_i = 0.0, pk_e = 0.0;
+    int hr_i = -1, hr_e = -1;
+    int h = d0 * 24;
+    for (int d = d0; d < d1; d++, p += 6 * qs) {
+        double v[24];
+        if constexpr (sizeof(V) == 4) {
+            f32x4 x[6];
+#pragma unroll
+            for (int q = 0; q < 6; q++) x[q] = *reinterpret_cast<const f32x4*>(p + q * qs);
+#pragma unroll
+            for (int q = 0; q < 6; q++)
+#pragma unroll
+                for (int u = 0; u < 4; u++) v[4 * q + u] = (double)x[q][u];
+        } else {
+            double2 x[12];
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                x[2 * q] = *reinterpret_cast<const double2*>(p + q * qs);
+                x[2 * q + 1] = *reinterpret_cast<const double2*>(p + q * qs + 2);
+            }
+#pragma unroll
+            for (int q = 0; q < 12; q++) { v[2 * q] = x[q].x; v[2 * q + 1] = x[q].y; }
+        }
+#pragma unroll
+        for (int u = 0; u < 24; u++, h++) {
+            const double a = v[u], b = -a;
+            imp += a > 0.0 ? a : 0.0;
+            ex += a < 0.0 ? b : 0.0;
+            if (a > pk_i) { pk_i = a; hr_i = h; }
+            if (b > pk_e) { pk_e = b; hr_e = h; }
+        }
+    }
+    const int64_t o = (int64_t)m * n + i;
+    if (out.import_kwh) out.import_kwh[o] = imp;
+    if (out.export_kwh) out.export_kwh[o] = ex;
+    if (out.peak_import_kw) out.peak_import_kw[o] = pk_i;
+    if (out.peak_export_kw) out.peak_export_kw[o] = pk_e;
+    if (out.peak_import_hour) out.peak_import_hour[o] = hr_i;
+    if (out.peak_export_hour) out.peak_export_hour[o] = hr_e;
+}
+
 #ifndef DGEN_TU_SEARCH
 // ===========================================================================
 // Certified Brent paths (round 6).  k_size bills from re-associated sums (the
@@ -7746,6 +7808,35 @@ int32_t dgen_finance_series(dgen_ctx* c, const dgen_outputs* O, const int32_t* l
     const int64_t total = 6 * n * NORM25;
     hipLaunchKernelGGL(k_finance_series, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, src, list_len, n, (int32_t)(MAXY + 1), out);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_plane_digest(dgen_ctx* c, const void* plane, int32_t plane_f64, int64_t n,
+                          const dgen_digest_out* out, void* stream) {
+    if (!c || !plane || !out || n < 0) {
+        set_err("dgen_plane_digest: bad argument (ctx %p, plane %p, out %p, n %lld)", (void*)c, plane,
+                (const void*)out, (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(plane) % 16 != 0) {
+        set_err("dgen_plane_digest: the plane must be 16-byte aligned (hour quads are loaded whole)");
+        return DGEN_E_ARG;
+    }
+    const int64_t blocks = (n + DG_BLOCK - 1) / DG_BLOCK;
+    if (blocks > 0x7fffffff) {
+        set_err("dgen_plane_digest: n = %lld exceeds the launch grid", (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const dim3 grid((unsigned)blocks, 12);
+    if (plane_f64)
+        hipLaunchKernelGGL((k_plane_digest<double>), grid, dim3(DG_BLOCK), 0, (hipStream_t)stream,
+                           (const double*)plane, n, *out);
+    else
+        hipLaunchKernelGGL((k_plane_digest<float>), grid, dim3(DG_BLOCK), 0, (hipStream_t)stream,
+                           (const float*)plane, n, *out);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

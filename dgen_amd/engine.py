@@ -607,6 +607,35 @@ class Engine:
         self._keep["_seq"] = (r, so)          # alive until the next call (stream order)
         return out
 
+    def plane_digest(self, plane, want=tuple(_lib.DIGEST_FIELDS)) -> Dict[str, object]:
+        """Per-agent monthly grid-exchange digest of one hourly plane
+        (dgen_plane_digest; async on the current stream).  plane: a tiled
+        [NH/4, n, 4] float32 / float64 device tensor as alloc_outputs makes it;
+        want: the members to compute (_lib.DIGEST_FIELDS).  Returns a dict of
+        [12, n] device tensors, month-major: import_kwh, export_kwh,
+        peak_import_kw, peak_export_kw (float64) and peak_import_hour,
+        peak_export_hour (int32 hour of year, -1 = none)."""
+        torch = _torch()
+        want = tuple(want)
+        bad = [k for k in want if k not in _lib.DIGEST_FIELDS]
+        if bad or not want:
+            raise ValueError(f"plane_digest: want must name members of {_lib.DIGEST_FIELDS} (got {want})")
+        if not isinstance(plane, torch.Tensor) or plane.device != self.dev:
+            raise TypeError("plane_digest: the plane must be a tensor on the engine's device")
+        if plane.dtype not in (torch.float32, torch.float64):
+            raise TypeError("plane_digest: the plane must be float32 or float64")
+        if plane.dim() != 3 or plane.shape[0] != _lib.NH // 4 or plane.shape[2] != 4 or not plane.is_contiguous():
+            raise ValueError(f"plane_digest: the plane must be contiguous hour-quad tiles [{_lib.NH // 4}, n, 4]")
+        n = int(plane.shape[1])
+        res = {k: torch.empty((12, n), dtype=torch.float64 if k in _lib.DIGEST_F64 else torch.int32,
+                              device=self.dev) for k in want}
+        if n == 0:
+            return res
+        co = _lib.DigestOut(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(self.lib.dgen_plane_digest(self.ctx, _ptr(plane), int(plane.dtype == torch.float64), n,
+                                              ctypes.byref(co), self.stream_handle()), "dgen_plane_digest")
+        return res
+
     def brent_selftest(self, lo, hi, xatol, c2, x0, c1, maxn=64):
         torch = _torch()
         f = lambda v: self._to_dev(np.asarray(v, dtype=np.float64), torch.float64)

@@ -190,19 +190,23 @@ def _device_tables(eng, src: ProfileStore, b: PopulationBuilder):
     eng.set_switches(b.switches.array())
 
 
-def agent_device_bytes(eng) -> int:
+def agent_device_bytes(eng, grid_metrics: bool = False) -> int:
     """HBM one agent of a drop-in call holds while it is sized: the three fp64
-    hourly planes (3 x 8760 x 8 B), its share of the workspace (bins, scratch
-    plane, split records: dgen_workspace_bytes at a scratch slot per agent),
-    the yearly and scalar outputs twice (the caller-order gather before the
-    download) and the agent columns."""
+    hourly planes (3 x 8760 x 8 B; every hourly mode computes them, and
+    grid_metrics digests them in place whatever the mode), its share of the
+    workspace (bins, scratch plane, split records: dgen_workspace_bytes at a
+    scratch slot per agent), the yearly and scalar outputs twice (the
+    caller-order gather before the download) and the agent columns.
+    grid_metrics: plus one plane's monthly digest (12 x (4 x 8 + 2 x 4) B) and
+    the 18 annual columns twice (the gather)."""
     k = 4096
     ws = int(eng.lib.dgen_workspace_bytes(k, k)) // k
     yearly = len(_lib.OUTPUT_YEARLY) * (_lib.MAXY + 1) * 8
-    return 3 * NH * 8 + ws + 2 * (yearly + 8 * len(_lib.OUTPUT_SCALARS)) + 8 * len(_lib.AGENT_COLUMNS)
+    gm = (12 * (4 * 8 + 2 * 4) + 2 * 18 * 8) if grid_metrics else 0
+    return 3 * NH * 8 + ws + 2 * (yearly + 8 * len(_lib.OUTPUT_SCALARS)) + 8 * len(_lib.AGENT_COLUMNS) + gm
 
 
-def device_rows_budget(eng, frac: float = 0.3) -> int:
+def device_rows_budget(eng, frac: float = 0.3, grid_metrics: bool = False) -> int:
     """Largest agent count one sizing call puts on the device at a time:
     ``DGEN_MAX_ROWS`` if set, else frac x (free HBM + this process's cached,
     unused blocks) / agent_device_bytes.  frac 0.3: two sub-batches are
@@ -219,12 +223,13 @@ def device_rows_budget(eng, frac: float = 0.3) -> int:
     share = max(1, int(os.environ.get("DGEN_WORKERS_PER_DEVICE", "1").strip() or 1))
     free, _total = torch.cuda.mem_get_info(eng.dev)
     spare = torch.cuda.memory_reserved(eng.dev) - torch.cuda.memory_allocated(eng.dev)
-    return max(1024, int(frac / share * (free + max(spare, 0)) / agent_device_bytes(eng)))
+    return max(1024, int(frac / share * (free + max(spare, 0)) / agent_device_bytes(eng, grid_metrics)))
 
 
 def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
-                hourly_device: bool = False, max_rows: Optional[int] = None):
+                hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
+                keep_planes: bool = True):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -236,14 +241,18 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     sub-batches are on the device at once: sub-batch k sizes while k - 1's
     planes download, and k waits for k - 2's.  hourly_device with more than
     one sub-batch: the planes come to the host instead (keeping every
-    sub-batch's planes in HBM would undo the bound)."""
+    sub-batch's planes in HBM would undo the bound).  grid_metrics: each
+    sub-batch also digests its planes on the device (grid_metrics.COLUMNS,
+    per-agent values: the bits of one call); keep_planes False: the planes
+    are released after that and never downloaded (o[plane] is None)."""
     n = len(cols["load_kwh"])
     if max_rows is None:
-        max_rows = device_rows_budget(get_engine())
+        max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics)
     max_rows = max(1, int(max_rows))
     import torch
     try:
-        return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows)
+        return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
+                                grid_metrics, keep_planes)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -251,13 +260,16 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
         if smaller < 1024:
             raise
         torch.cuda.empty_cache()
-        return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller)
+        return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
+                           grid_metrics=grid_metrics, keep_planes=keep_planes)
 
 
-def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int):
+def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
+                     grid_metrics: bool = False, keep_planes: bool = True):
     n = len(cols["load_kwh"])
     if n <= max_rows:
-        return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device)
+        return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
+                                grid_metrics, keep_planes)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -271,7 +283,8 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         sub = {k: v[lo:hi] for k, v in cols.items()}
         nw = None if net_weights is None else tuple(np.asarray(w)[lo:hi] for w in net_weights)
         tm: dict = {}
-        parts.append(_run_device_once(b, sub, src, tm, nw, hourly_async=True, hourly_device=False))
+        parts.append(_run_device_once(b, sub, src, tm, nw, hourly_async=True, hourly_device=False,
+                                      grid_metrics=grid_metrics, keep_planes=keep_planes))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -279,7 +292,14 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_YEARLY:
         o[name] = np.concatenate([p[name] for p in parts])
+    if grid_metrics:
+        from .grid_metrics import COLUMNS
+        for name in COLUMNS:
+            o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
+        if not keep_planes:
+            o[name] = None
+            continue
         segs = _Segments([(p[name], np.arange(p[name].n, dtype=np.int64), None, False) for p in parts])
         if hourly_async or hourly_device:
             o[name] = segs
@@ -297,13 +317,16 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
 
 def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
-                     hourly_device: bool = False):
+                     hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True):
     """Size the batch in one device call; net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
     summed on the device from the planes in place (k_state_hourly, one
     segment, fixed order) instead of a host loop over the agents.
     hourly_async: the three hourly planes come back as engine.HostPlane
-    (downloading on a background thread), everything else at once."""
+    (downloading on a background thread), everything else at once.
+    grid_metrics: o also holds grid_metrics.COLUMNS, the annual grid-exchange
+    digest of the three planes taken on the device (caller order); keep_planes
+    False then releases the planes without a download (o[plane] is None)."""
     import time
     import torch
     from .attachment import state_hourly
@@ -325,6 +348,18 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         pv = out["net_pvonly"]
         net = state_hourly(eng, (out["baseline"], pv, pv), (na, torch.zeros_like(na), nn), None,
                            [0, batch.n])[0] * 1000.0
+    gm = None
+    if grid_metrics:
+        from .grid_metrics import annual_columns
+        inv = None
+        if batch.perm is not None:
+            iv = np.empty(batch.n, np.int64)
+            iv[batch.perm] = np.arange(batch.n, dtype=np.int64)
+            inv = eng._to_dev(iv, torch.int64)
+        gm = annual_columns(eng, out, inv)
+        if not keep_planes:
+            for name in _lib.OUTPUT_HOURLY:
+                out[name] = None
     torch.cuda.synchronize(eng.dev)
     t2 = time.perf_counter()
     o = outputs_to_host(out, batch.perm, hourly_async=hourly_async, hourly_device=hourly_device)
@@ -336,6 +371,8 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
                 v[unsized] = np.nan
     if net is not None:
         o["net_sum_kw"] = net.cpu().numpy()
+    if gm is not None:           # after the unsized rows' NaNs: their no-system planes digest like any other
+        o.update(gm)
     if timing is not None:
         timing.update(upload_s=t1 - t0, device_s=t2 - t1, download_s=time.perf_counter() - t2)
     return o
@@ -446,7 +483,8 @@ def _yearly_lists(a: np.ndarray, n1: np.ndarray, fmt: str = "list"):
 
 
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
-               timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None):
+               timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
+               grid_metrics: bool = False):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -470,7 +508,13 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     timing: filled with the host / device phases (seconds).  max_rows: the
     most agents on the device at once (default device_rows_budget(): a frame
     larger than free HBM allows is sized in consecutive sub-batches with the
-    same outputs, _run_device)."""
+    same outputs, _run_device).  grid_metrics: the frame gains the 18 scalar
+    columns grid_metrics.COLUMNS -- per case (baseline, pvonly, with_batt) the
+    annual grid_import_kwh_ / grid_export_kwh_ / peak_import_kw_ /
+    peak_export_kw_ (float) and peak_import_hour_ / peak_export_hour_ (int
+    hour of year, -1 = none) -- digested from the fp64 planes on the device
+    (dgen_plane_digest), the same bits in every hourly mode and sub-batching;
+    with hourly="none" the planes then never leave HBM."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
@@ -482,7 +526,8 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     t1 = time.perf_counter()
     dev_t: dict = {}
     o = _run_device(b, cols, src, dev_t, net_weights, hourly_async=hourly in ("lazy", "array", "list"),
-                    hourly_device=hourly == "device", max_rows=max_rows)
+                    hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
+                    keep_planes=not (grid_metrics and hourly == "none"))
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -547,6 +592,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     out["cash_flow"] = ycol(o["cash_flow"])
     out["batt_kw"] = o["batt_kw"]
     out["batt_kwh"] = o["batt_kwh"]
+    if grid_metrics:
+        from .grid_metrics import COLUMNS
+        for name in COLUMNS:
+            out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:
         # download_wait_s: time the frame assembly waited for the hourly planes
@@ -556,9 +605,11 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 
 
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
-               hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None):
+               hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
+               grid_metrics: bool = False):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
-    agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt)."""
+    agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
+    grid_metrics: size_frame's 18 per-agent grid-exchange columns."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -571,7 +622,7 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     # on the device; the reference's running sum in agent order and the
     # kernel's fixed-order tree agree to rounding (parity test: 1e-12 relative)
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
-                           net_weights=(n_adopt, n_non), max_rows=max_rows)
+                           net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

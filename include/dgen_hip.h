@@ -709,6 +709,30 @@ int32_t dgen_set_exact(dgen_ctx* ctx, int32_t mode);
  * (synchronises the ctx's stream work of that call).                         */
 int32_t dgen_exact_count(dgen_ctx* ctx, int64_t* out);
 
+/* Per-agent monthly grid-exchange digest of one hourly plane (additive to
+ * ABI 14).  `plane` is one of dgen_size_agents' hourly planes in its hour-quad
+ * tiles ((h, i) at ((h / 4) * n + i) * 4 + h % 4; float, or double when
+ * plane_f64 is set; DGEN_NH hours).  For agent i and calendar month m (hours
+ * [h0, h1) of the non-leap year, the scan's month table), in hour order:
+ *   imp = exp = pk_i = pk_e = 0.0;  hr_i = hr_e = -1
+ *   v = (double)plane[h, i]
+ *   if v > 0:      imp += v;   if  v > pk_i: pk_i =  v, hr_i = h
+ *   else if v < 0: exp += -v;  if -v > pk_e: pk_e = -v, hr_e = h
+ * fp64 sums, strictly sequential in hour order; the first hour wins a tie; a
+ * NaN hour fails both comparisons and adds nothing.  One lane per (agent,
+ * month), no atomics and no cross-lane traffic: run-to-run identical.  The
+ * outputs are month-major [12][n] -- the k = 12 plane-major planes
+ * dgen_segment_sums takes.  A NULL member is not written.  Replaces nothing in
+ * the reference (it drops the hourly lists before agent_outputs,
+ * dgen_model.py:441-458, and derives no per-agent grid exchange).            */
+typedef struct {            /* each [12][n], month-major: value (m, i) at [m * n + i]; any may be NULL */
+    double  *import_kwh, *export_kwh, *peak_import_kw, *peak_export_kw;
+    int32_t *peak_import_hour, *peak_export_hour;   /* hour of year 0..8759, -1 = none */
+} dgen_digest_out;
+
+int32_t dgen_plane_digest(dgen_ctx* ctx, const void* plane, int32_t plane_f64, int64_t n,
+                          const dgen_digest_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
