@@ -110,6 +110,17 @@ class DigestOut(ctypes.Structure):
     _fields_ = [(name, _vp) for name in DIGEST_FIELDS]
 
 
+CURVE_F64 = ["npv", "payback_raw", "first_with", "first_without", "total_cost"]
+CURVE_I32 = ["tariff", "switched", "status"]
+CURVE_FIELDS = CURVE_F64 + CURVE_I32
+CURVE_MAX_POINTS = 64   # include/dgen_hip.h dgen_objective_curve: 1 <= K <= 64
+
+
+class CurveOut(ctypes.Structure):
+    """dgen_curve_out: [K][n] point-major device planes, any may be NULL."""
+    _fields_ = [(name, _vp) for name in CURVE_FIELDS]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -127,7 +138,7 @@ EXPORTED = [
     "dgen_kernel_times", "dgen_last_paths", "dgen_set_dc_prebuild", "dgen_segment_sums", "dgen_max_market_share", "dgen_diffusion",
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
-    "dgen_plane_digest",
+    "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve",
 ]
 
 
@@ -207,6 +218,12 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_rows_seq_sum.argtypes = [_vp, _vp, _i64, _vp, _i64, _vp, _vp]
     L.dgen_plane_digest.restype = _i32
     L.dgen_plane_digest.argtypes = [_vp, _vp, _i32, _i64, ctypes.POINTER(DigestOut), _vp]
+    L.dgen_eval_agents.restype = _i32
+    L.dgen_eval_agents.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents),
+                                   ctypes.POINTER(Outputs), _vp, _i64, _vp, ctypes.c_size_t, _i64, _vp]
+    L.dgen_objective_curve.restype = _i32
+    L.dgen_objective_curve.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _vp, _i32, _i64,
+                                       ctypes.POINTER(CurveOut), _vp, ctypes.c_size_t, _i64, _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

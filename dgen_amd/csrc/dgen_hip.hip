@@ -57,6 +57,15 @@
 #ifndef DGEN_NO2_FIN_PK
 #define DGEN_NO2_FIN_PK 0
 #endif
+#ifndef DGEN_NO2_EVAL
+#define DGEN_NO2_EVAL 0
+#endif
+#ifndef DGEN_NO2_EVAL_DC
+#define DGEN_NO2_EVAL_DC 0
+#endif
+#ifndef DGEN_NO2_EVAL_PK
+#define DGEN_NO2_EVAL_PK 0
+#endif
 
 namespace {
 
@@ -3972,9 +3981,233 @@ k_size_w(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t n, 
     PH_CNT(9, nfev, sl == 0);
 }
 #endif
+
+// Evaluation at caller-given sizes (dgen_eval_agents, dgen_objective_curve):
+// k_size_w's year-lane objective without the search around it.  xs holds K
+// points per agent, point-major [K][n]; every point is one
+// calc_system_performance(x, en_batt=False) from the agent's initial tariff
+// state (tariff0, not switched) -- the rate switch's stickiness belongs to one
+// search's sequence of evaluations and does not carry between unrelated sizes.
+// The prologue is k_size_w's own (a copy: that kernel's 32-lane NEM
+// instantiation sits at its register cap, DESIGN.md section 8, and stays as it
+// is); the bracket is formed only so that DGEN_ST_BOUNDS keeps its meaning.
+// The generation-scale range of the net-billing split and the demand
+// envelopes is the point's own (its kW over the years' degradation), so a
+// point's result does not depend on the other points asked for with it: the
+// split's sums are re-associated by the range (which hours stay on one side
+// over it), and column k of a curve is a K = 1 call at xs[k] bit for bit only
+// with the same range.  The records are therefore rebuilt per point, inside
+// the evaluation that first bills the tariff; no prebuild kernel runs (theirs
+// is the bracket's range).  A point that is not finite or not positive gets
+// DGEN_ST_BOUNDS and NaN.
+// full: K = 1 and the outputs are k_size_w's, written to O (system_kw =
+// x_last = x, nfev = 1); else the curve's members, [K][n] each.
+template <int LPA, bool DC, bool NET, bool PK>
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(DC ? 2 : 3)))
+k_eval_w(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t n, int64_t i0, int64_t i1,
+         void* dcws, char* nbws, const double* __restrict__ xs, int K, dgen_curve_out C, int full)
+#ifdef DGEN_TU_MAIN
+;
+#else
+{
+    const int lane = threadIdx.x;
+    const int64_t i = i0 + (int64_t)blockIdx.x * (WAVE / LPA) + (LPA == WAVE ? 0 : lane / LPA);
+    if (i >= i1) return;
+    const int half = lds_half(T.max_periods);
+    YCtx<LPA> c(lane);
+    const int sl = c.g.sl;
+    c.y = sl + 1;
+    c.S = ylds_make(dyn_lds, half, c.g, PK && T.peak_units != 0, yl_mode<DC, NET>());
+    c.tariffs = T.tariffs;
+    c.dem_table = T.demand;
+    c.n_dem = T.n_demand;
+    c.dem = nullptr;
+    c.dc_on = cfg.skip_demand_charges == 0;
+    c.dem_bill = false;
+    c.pk13 = false;
+    c.dem_wo_pending = false;
+    c.env_ok = false;
+    c.env.lines = nullptr;
+    c.stg = nullptr;
+    c.stg_ok = false;
+    c.env_tag = 0;
+    c.dc_nq = (T.max_dc_periods > 0 && T.max_dc_periods <= DCP) ? T.max_dc_periods : DCP;
+    if constexpr (DC) {
+        if (dcws) c.env = dc_env_at(dcws, i);
+        c.stg = reinterpret_cast<DcStage*>(reinterpret_cast<char*>(dyn_lds) +
+                                           ylds_bytes(half, LPA, PK && T.peak_units != 0, yl_mode<DC, NET>())) + lane / LPA;
+    }
+    {
+        const int slot = A.scratch_slot[i];
+        c.nb = (nbws && slot >= 0) ? nbws + (size_t)slot * NB_BYTES : nullptr;
+        c.nb_ok = false;
+        c.nb_tag = 0;
+        c.nb_pending = false;
+    }
+    c.sw_rows = T.switches + A.sw_solar_off[i];
+    c.sw_cnt = A.sw_solar_cnt[i];
+    c.status = 0;
+    c.switched = 0;
+    const uint8_t fl = A.flags[i];
+    const bool is_res = (fl & 1) != 0, is_ca = (fl & 2) != 0;
+    c.N = A.econ_life[i];
+    c.active = c.y <= c.N;
+    c.kwh = A.load_kwh[i];
+    c.capex = A.capex[i];
+    c.ccm = A.ccm[i];
+    c.yearend = cfg.nm_yearend_sell_rate;
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const int t0 = A.tariff0[i];
+    const double naep0 = T.cf_naep[cr];
+    c.load_scale = c.kwh / T.shape_sum[lr];
+    c.lslots = T.shape_slots + (int64_t)lr * NSLOT;
+    c.gslots = T.cf_slots + (int64_t)cr * NSLOT;
+    const double rate_base = 1.0 + (A.inflation[i] * 100.0) * 0.01 + (A.escalator[i] * 100.0) * 0.01;
+    const double sys_base = 1.0 - (A.pv_deg[i] * 100.0) * 0.01;
+    c.r_y = pow_seq(rate_base, c.y - 1);
+    c.s_y = pow_seq(sys_base, c.y - 1);
+    c.loan = yl_make_loan(A, cfg, i, c.N, is_res, c.y);
+    c.src.shape = T.shapes + (int64_t)lr * NH;
+    c.src.cf = T.cfs + (int64_t)cr * NH;
+    c.src.sysgen = nullptr;
+    c.src.sys_stride = 0;
+    c.src.load_scale = c.load_scale;
+    c.src.gen_scale = 0.0;
+    const int wr = A.wholesale_row[i];
+    c.ts_row = (!is_ca && wr >= 0 && T.wholesale) ? T.wholesale + (int64_t)wr * NH : nullptr;
+    c.src.ts = nullptr;                       // set per tariff (yl_set_tariff)
+    c.src.ts_mult = A.price_mult[i];
+
+    bool bad = false;
+    if (c.N < 1 || c.N > MAXY || c.N > LPA) { c.status |= DGEN_ST_YEARS; bad = true; }
+    if (t0 < 0 || t0 >= T.n_tariffs) { c.status |= DGEN_ST_TARIFF; bad = true; }
+    // kWh/kW tier units without the demand machinery: unsized, per agent (k_size_w)
+    else if ((T.tariffs[t0].flags & DGEN_ST_UNIT) ||
+             (peak_unit(T.tariffs[t0]) &&
+              !(PK && T.peak_units && tariff_peaks(T.demand, T.n_demand, T.tariffs[t0])))) {
+        c.status |= DGEN_ST_UNIT;
+        bad = true;
+    }
+    const double max_load = c.kwh / naep0;                         // ff:440-444
+    const double low = max_load * 0.8, high = max_load * 1.25;
+    if (!isfinite(low) || !isfinite(high)) { c.status |= DGEN_ST_BOUNDS; bad = true; }
+    if (c.kwh == 0.0) c.status |= DGEN_ST_ZERO_LOAD;
+    if (full) {                                      // K = 1: an invalid size is an unsized agent
+        const double x = xs[i];
+        if (!(isfinite(x) && x > 0.0)) { c.status |= DGEN_ST_BOUNDS; bad = true; }
+    }
+    const int64_t row = i * (MAXY + 1);
+    if (bad && full) {
+        if (sl == 0) {
+            O.status[i] = c.status;
+            O.nfev[i] = 0;
+            O.system_kw[i] = NAN; O.x_last[i] = NAN; O.npv[i] = NAN;
+            O.payback_raw[i] = NAN; O.payback_period[i] = NAN;
+            O.first_with[i] = NAN; O.first_without[i] = NAN; O.price_per_kwh[i] = NAN;
+            O.tariff_final[i] = t0; O.switched[i] = 0;
+        }
+        for (int k = sl; k <= MAXY; k += LPA) {
+            O.cash_flow[row + k] = NAN; O.cfev_pv[row + k] = NAN;
+            O.bill_w_pv[row + k] = NAN; O.bill_wo_pv[row + k] = NAN;
+        }
+        return;
+    }
+    auto curve_nan = [&](int64_t at, int status) __attribute__((always_inline)) {
+        if (C.npv) C.npv[at] = NAN;
+        if (C.payback_raw) C.payback_raw[at] = NAN;
+        if (C.first_with) C.first_with[at] = NAN;
+        if (C.first_without) C.first_without[at] = NAN;
+        if (C.total_cost) C.total_cost[at] = NAN;
+        if (C.tariff) C.tariff[at] = t0;
+        if (C.switched) C.switched[at] = 0;
+        if (C.status) C.status[at] = status;
+    };
+    if (bad) {
+        if (sl == 0)
+            for (int k = 0; k < K; k++) {
+                const double x = xs[(int64_t)k * n + i];
+                curve_nan((int64_t)k * n + i, c.status | ((isfinite(x) && x > 0.0) ? 0 : DGEN_ST_BOUNDS));
+            }
+        return;
+    }
+    const int ln = (c.N >= 1 && c.N <= LPA) ? c.N - 1 : 0;
+    const double sN = c.g.bcast(c.s_y, ln);
+    const double s_lo = sN < 1.0 ? sN : 1.0, s_hi = sN > 1.0 ? sN : 1.0;
+    const int status0 = c.status | T.tariffs[t0].flags;
+    bool fresh = false;                               // the initial tariff is set
+    for (int k = 0; k < K; k++) {
+        const int64_t at = (int64_t)k * n + i;
+        const double x = xs[at];
+        if (!(isfinite(x) && x > 0.0)) {              // curve form only (full: `bad` above)
+            if (sl == 0) curve_nan(at, status0 | DGEN_ST_BOUNDS);
+            continue;
+        }
+        // generation-scale range of this point over the years' degradation
+        // (envelopes, net-billing split): the records of another point's
+        // range are dropped
+        const double kws = ((x * 1000.0) * 0.96) / 1000.0;
+        c.tlo = kws * s_lo;
+        c.thi = kws * s_hi;
+        c.nb_tag = 0;
+        c.env_tag = 0;
+        // the point starts from the agent's initial tariff state; the bins and
+        // the no-system bill of a bins-only tariff the last point left in
+        // place are that state already
+        c.status = status0;
+        c.switched = 0;
+        if (!fresh || c.tariff != t0 || net_hourly(*c.tp) || c.dem != nullptr) {
+            yl_set_tariff<LPA, DC, NET, PK>(c, t0);
+            fresh = true;
+        }
+        (void)yl_objective<LPA, DC, NET, PK>(c, x);
+        const YLast& l = c.last;
+        const YFlow& f = l.flow;
+        const double w1 = c.g.bcast(l.w, 0);
+        if (full) {
+            if (sl == 0) {
+                O.cash_flow[row] = -l.total;
+                O.cfev_pv[row] = 0.0;
+                O.bill_w_pv[row] = 0.0;
+                O.bill_wo_pv[row] = 0.0;
+            }
+            if (c.active) {
+                O.cash_flow[row + c.y] = f.pb;
+                O.cfev_pv[row + c.y] = l.ev;
+                O.bill_w_pv[row + c.y] = l.w;
+                O.bill_wo_pv[row + c.y] = l.wo;
+            }
+            if (sl == 0) {
+                O.npv[i] = f.npv;
+                O.payback_raw[i] = f.payback;
+                double pb = isfinite(f.payback) ? f.payback : 30.1;
+                O.payback_period[i] = rint(pb * 10.0) / 10.0;
+                O.first_with[i] = w1;
+                O.first_without[i] = c.wo1;
+                O.price_per_kwh[i] = c.wo1 / c.kwh;
+                O.system_kw[i] = x;
+                O.x_last[i] = x;
+                O.nfev[i] = 1;
+                O.tariff_final[i] = c.tariff;
+                O.switched[i] = c.switched;
+                O.status[i] = c.status;
+            }
+        } else if (sl == 0) {
+            if (C.npv) C.npv[at] = f.npv;
+            if (C.payback_raw) C.payback_raw[at] = f.payback;
+            if (C.first_with) C.first_with[at] = w1;
+            if (C.first_without) C.first_without[at] = c.wo1;
+            if (C.total_cost) C.total_cost[at] = l.total;
+            if (C.tariff) C.tariff[at] = c.tariff;
+            if (C.switched) C.switched[at] = c.switched;
+            if (C.status) C.status[at] = c.status;
+        }
+    }
+}
+#endif
 }  // namespace dgen_srch
 namespace {
 using dgen_srch::k_size_w;
+using dgen_srch::k_eval_w;
 
 // The tariff an agent bills its first Brent evaluation with: scipy's first
 // point a + golden_mean (b - a) (brent_bounded) through the solar rate switch
@@ -6537,6 +6770,27 @@ DGEN_INST_SIZE(64, true, true, false)
 DGEN_INST_SIZE(64, true, false, false)
 DGEN_INST_SIZE(64, true, true, true)
 #undef DGEN_INST_SIZE
+#define DGEN_INST_EVAL(L, D, N, P)                                                                       \
+    template __global__ void k_eval_w<L, D, N, P>(dgen_tables, dgen_agents, dgen_outputs, dgen_cfg,   \
+                                                  int64_t, int64_t, int64_t, void*, char*, const double*, \
+                                                  int, dgen_curve_out, int);
+#if !DGEN_NO2_EVAL
+DGEN_INST_EVAL(32, false, false, false)
+DGEN_INST_EVAL(32, false, true, false)
+#endif
+#if !DGEN_NO2_EVAL_DC
+DGEN_INST_EVAL(32, true, true, false)
+DGEN_INST_EVAL(32, true, false, false)
+#endif
+#if !DGEN_NO2_EVAL_PK
+DGEN_INST_EVAL(32, true, true, true)
+#endif
+DGEN_INST_EVAL(64, false, false, false)
+DGEN_INST_EVAL(64, false, true, false)
+DGEN_INST_EVAL(64, true, true, false)
+DGEN_INST_EVAL(64, true, false, false)
+DGEN_INST_EVAL(64, true, true, true)
+#undef DGEN_INST_EVAL
 template __global__ void k_dc_env<2>(dgen_tables, dgen_agents, dgen_cfg, int64_t, int64_t, void*);
 template __global__ void k_dc_env<4>(dgen_tables, dgen_agents, dgen_cfg, int64_t, int64_t, void*);
 template __global__ void k_dc_env<DGEN_DCP>(dgen_tables, dgen_agents, dgen_cfg, int64_t, int64_t, void*);
@@ -6807,14 +7061,12 @@ size_t dgen_workspace_bytes(int64_t n, int64_t n_scratch) {
            NB_BYTES * (size_t)n_scratch;
 }
 
-int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A,
-                         const dgen_outputs* O, int64_t n, void* ws, size_t ws_bytes,
-                         int64_t n_scratch, void* stream) {
-    if (!c || !T || !A || !O) { set_err("dgen_size_agents: null argument"); return DGEN_E_ARG; }
-    if (n <= 0) return DGEN_OK;
+// The table and agent-column checks of the entry points that run the
+// year-lane kernels (`who` names the entry in the message).
+static int32_t yl_check_args(const dgen_tables* T, const dgen_agents* A, const char* who) {
     if (!T->shapes || !T->shape_sum || !T->shape_slots || !T->cfs || !T->cf_naep || !T->cf_slots ||
         !T->tariffs || T->n_tariffs <= 0 || T->n_demand < 0 || (T->n_demand > 0 && !T->demand)) {
-        set_err("dgen_size_agents: incomplete tables");
+        set_err("%s: incomplete tables", who);
         return DGEN_E_ARG;
     }
     const void* req_a[] = {A->load_row, A->cf_row, A->wholesale_row, A->tariff0, A->sw_solar_off,
@@ -6824,52 +7076,21 @@ int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A
                            A->real_discount, A->itc_frac, A->capex, A->capex_combined,
                            A->batt_capex_kwh, A->ccm, A->vor};
     for (const void* p : req_a)
-        if (!p) { set_err("dgen_size_agents: missing agent column"); return DGEN_E_ARG; }
-    const void* req_o[] = {O->system_kw, O->x_last, O->annual_kwh, O->naep, O->capacity_factor,
-                           O->price_per_kwh, O->npv, O->payback_raw, O->payback_period,
-                           O->first_with, O->first_without, O->batt_kw, O->batt_kwh,
-                           O->npv_pv_batt, O->nfev, O->tariff_final, O->switched, O->status,
-                           O->cash_flow, O->cfev_pv, O->bill_w_pv, O->bill_wo_pv, O->cfev_batt,
-                           O->bill_w_batt, O->bill_wo_batt};
-    for (const void* p : req_o)
-        if (!p) { set_err("dgen_size_agents: missing output column"); return DGEN_E_ARG; }
-    // WO: the with-battery plane alone (float32 tiles; daily plan, no loss
-    // model, no demand machinery): the model-year loop's export form
-    const bool wo = O->baseline == nullptr && O->net_pvonly == nullptr && O->net_with_batt != nullptr;
-    const bool hourly = O->baseline != nullptr;
-    if (!wo && ((O->net_pvonly != nullptr) != hourly || (O->net_with_batt != nullptr) != hourly)) {
-        set_err("dgen_size_agents: hourly planes must be all set, all NULL, or the with-battery plane alone");
-        return DGEN_E_ARG;
-    }
-    if (wo && (O->hourly_f64 || c->cfg.batt_loss_model == 1 || c->cfg.batt_update_hours != 24)) {
-        set_err("dgen_size_agents: the with-battery plane alone is float32, daily plan, no loss model");
-        return DGEN_E_ARG;
-    }
-    // k_hourly_batt forms a 32-bit per-lane byte offset i x 16 into the hourly tiles
-    if (n >= ((int64_t)1 << 29) || n_scratch >= ((int64_t)1 << 28) ||
-        ((hourly || wo) && n >= ((int64_t)1 << (O->hourly_f64 ? 27 : 28)))) {
-        set_err("dgen_size_agents: batch too large (n < 2^29, n < 2^28 with f32 hourly planes, "
-                "2^27 with f64, n_scratch < 2^28 per call)");
-        return DGEN_E_ARG;
-    }
-    if (!ws || ws_bytes < dgen_workspace_bytes(n, n_scratch)) {
-        set_err("dgen_size_agents: workspace too small (%zu < %zu)", ws_bytes,
-                dgen_workspace_bytes(n, n_scratch));
-        return DGEN_E_ARG;
-    }
-    // the year-lane kernels keep the TOU demand peaks in the lane's LDS column
-    // (4 x half slots): with demand charges billed it must hold DGEN_DCP
-    dgen_tables Tk = *T;
+        if (!p) { set_err("%s: missing agent column", who); return DGEN_E_ARG; }
+    return DGEN_OK;
+}
+
+// The tables as the year-lane kernels take them (LDS column sized for the
+// demand periods and the net-billing stage) and the context's envelope
+// storage for n agents; *dc_out: the batch runs the demand machinery.
+static int32_t yl_prepare(dgen_ctx* c, dgen_tables& Tk, int64_t n, int64_t n_scratch, bool* dc_out) {
     // the demand machinery also supplies the month peaks of kWh/kW tier units
     const bool dc = (c->cfg.skip_demand_charges == 0 && Tk.n_demand > 0) || (Tk.peak_units && Tk.n_demand > 0);
-    if (wo && dc) {
-        set_err("dgen_size_agents: the with-battery plane alone is not built with demand charges / kWh/kW tiers");
-        return DGEN_E_ARG;
-    }
+    // the year-lane kernels keep the TOU demand peaks in the lane's LDS column
+    // (4 x half slots): with demand charges billed it must hold DGEN_DCP
     if (dc && 4 * lds_half(Tk.max_periods) < DCP) Tk.max_periods = (DCP + 3) / 4;
     // yl_bill_nb stages its entries and month sums in slots 2 half .. 2 half + 4
     if (n_scratch > 0 && lds_half(Tk.max_periods) < 3) Tk.max_periods = 3;
-    T = &Tk;
     HIP_TRY(hipSetDevice(c->device));
     if (dc && (size_t)n * DCW_BYTES > c->dc_cap) {   // envelope storage (context-owned)
         if (c->dc_buf) HIP_TRY(hipFree(c->dc_buf));
@@ -6882,9 +7103,122 @@ int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A
             c->dc_cap = (size_t)n * DCW_BYTES;
         }
     }
+    *dc_out = dc;
+    return DGEN_OK;
+}
+
+// k_eval_w over rows [i0, i1) of a batch of n (dgen_eval_agents' chunks, full
+// form; dgen_objective_curve): k_size_w's instantiation choice, with the
+// 32-lane builds the guard withdrew (DGEN_NO2_EVAL*) run one agent per wave.
+// nm: the leading rows below it hold no scratch slot (bins-only instantiation).
+static void launch_eval(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const dgen_outputs& O,
+                        int64_t n, int64_t i0, int64_t i1, int64_t nm, bool dc, int64_t n_scratch,
+                        char* nbws, const double* xs, int K, const dgen_curve_out& C, int full, hipStream_t s) {
+    const bool fits32 = A->max_years >= 1 && A->max_years <= 32;
+    const bool pk = dc && T->peak_units != 0;
+    const int lpa = (fits32 && !(pk ? DGEN_NO2_EVAL_PK : dc ? DGEN_NO2_EVAL_DC : DGEN_NO2_EVAL)) ? 32 : WAVE;
+    const int apw = WAVE / lpa;                       // agents per wave
+    const int half = lds_half(T->max_periods);
+    const size_t lds_nem = ylds_bytes(half, lpa, false, YL_NEM);
+    const size_t lds_dc = ylds_bytes(half, lpa, false, YL_DC) + (size_t)apw * DCS_BYTES;
+    const size_t lds_all = ylds_bytes(half, lpa, pk) + (dc ? (size_t)apw * DCS_BYTES : 0);
+    const bool net = n_scratch > 0;
+    const bool dc_net = T->no_net == 0;
+    auto grid = [&](int64_t a, int64_t b) { return dim3((unsigned)((b - a + apw - 1) / apw)); };
+#define DGEN_EVAL_LAUNCH(L, D, N, P, LDS, a, b, dcws)                                                     \
+    hipLaunchKernelGGL((k_eval_w<L, D, N, P>), grid(a, b), dim3(WAVE), LDS, s, *T, *A, O, c->cfg, n, a, b, \
+                       dcws, nbws, xs, K, C, full)
+#define DGEN_EVAL_NEM(L)                                                                                  \
+    do {                                                                                                  \
+        if (net) {                                                                                        \
+            if (nm > i0) DGEN_EVAL_LAUNCH(L, false, false, false, lds_nem, i0, nm, nullptr);              \
+            if (i1 > nm) DGEN_EVAL_LAUNCH(L, false, true, false, lds_all, nm, i1, nullptr);               \
+        } else                                                                                            \
+            DGEN_EVAL_LAUNCH(L, false, false, false, lds_nem, i0, i1, nullptr);                           \
+    } while (0)
+#define DGEN_EVAL_DC(L)                                                                                   \
+    do {                                                                                                  \
+        if (dc_net) DGEN_EVAL_LAUNCH(L, true, true, false, lds_all, i0, i1, c->dc_buf);                   \
+        else DGEN_EVAL_LAUNCH(L, true, false, false, lds_dc, i0, i1, c->dc_buf);                          \
+    } while (0)
+#define DGEN_EVAL_PK(L) DGEN_EVAL_LAUNCH(L, true, true, true, lds_all, i0, i1, c->dc_buf)
+    if (lpa == 32 && !dc) {
+#if !DGEN_NO2_EVAL
+        DGEN_EVAL_NEM(32);
+#endif
+    } else if (lpa == 32 && !pk) {
+#if !DGEN_NO2_EVAL_DC
+        DGEN_EVAL_DC(32);
+#endif
+    } else if (lpa == 32) {
+#if !DGEN_NO2_EVAL_PK
+        DGEN_EVAL_PK(32);
+#endif
+    } else if (!dc) {
+        DGEN_EVAL_NEM(WAVE);
+    } else if (!pk) {
+        DGEN_EVAL_DC(WAVE);
+    } else {
+        DGEN_EVAL_PK(WAVE);
+    }
+#undef DGEN_EVAL_NEM
+#undef DGEN_EVAL_DC
+#undef DGEN_EVAL_PK
+#undef DGEN_EVAL_LAUNCH
+}
+
+// dgen_size_agents (kw == nullptr: the bounded search) and dgen_eval_agents
+// (one evaluation at kw[i]): the same checks, chunk pipeline, hourly scan and
+// battery run around either kernel.
+static int32_t size_or_eval(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A,
+                            const dgen_outputs* O, const double* kw, int64_t n, void* ws, size_t ws_bytes,
+                            int64_t n_scratch, void* stream, const char* who) {
+    if (!c || !T || !A || !O) { set_err("%s: null argument", who); return DGEN_E_ARG; }
+    if (n <= 0) return DGEN_OK;
+    if (int32_t r = yl_check_args(T, A, who)) return r;
+    const void* req_o[] = {O->system_kw, O->x_last, O->annual_kwh, O->naep, O->capacity_factor,
+                           O->price_per_kwh, O->npv, O->payback_raw, O->payback_period,
+                           O->first_with, O->first_without, O->batt_kw, O->batt_kwh,
+                           O->npv_pv_batt, O->nfev, O->tariff_final, O->switched, O->status,
+                           O->cash_flow, O->cfev_pv, O->bill_w_pv, O->bill_wo_pv, O->cfev_batt,
+                           O->bill_w_batt, O->bill_wo_batt};
+    for (const void* p : req_o)
+        if (!p) { set_err("%s: missing output column", who); return DGEN_E_ARG; }
+    // WO: the with-battery plane alone (float32 tiles; daily plan, no loss
+    // model, no demand machinery): the model-year loop's export form
+    const bool wo = O->baseline == nullptr && O->net_pvonly == nullptr && O->net_with_batt != nullptr;
+    const bool hourly = O->baseline != nullptr;
+    if (!wo && ((O->net_pvonly != nullptr) != hourly || (O->net_with_batt != nullptr) != hourly)) {
+        set_err("%s: hourly planes must be all set, all NULL, or the with-battery plane alone", who);
+        return DGEN_E_ARG;
+    }
+    if (wo && (O->hourly_f64 || c->cfg.batt_loss_model == 1 || c->cfg.batt_update_hours != 24)) {
+        set_err("%s: the with-battery plane alone is float32, daily plan, no loss model", who);
+        return DGEN_E_ARG;
+    }
+    // k_hourly_batt forms a 32-bit per-lane byte offset i x 16 into the hourly tiles
+    if (n >= ((int64_t)1 << 29) || n_scratch >= ((int64_t)1 << 28) ||
+        ((hourly || wo) && n >= ((int64_t)1 << (O->hourly_f64 ? 27 : 28)))) {
+        set_err("%s: batch too large (n < 2^29, n < 2^28 with f32 hourly planes, "
+                "2^27 with f64, n_scratch < 2^28 per call)", who);
+        return DGEN_E_ARG;
+    }
+    if (!ws || ws_bytes < dgen_workspace_bytes(n, n_scratch)) {
+        set_err("%s: workspace too small (%zu < %zu)", who, ws_bytes, dgen_workspace_bytes(n, n_scratch));
+        return DGEN_E_ARG;
+    }
+    dgen_tables Tk = *T;
+    const bool dc_any = (c->cfg.skip_demand_charges == 0 && Tk.n_demand > 0) || (Tk.peak_units && Tk.n_demand > 0);
+    if (wo && dc_any) {
+        set_err("%s: the with-battery plane alone is not built with demand charges / kWh/kW tiers", who);
+        return DGEN_E_ARG;
+    }
+    bool dc = false;
+    if (int32_t r = yl_prepare(c, Tk, n, n_scratch, &dc)) return r;
+    T = &Tk;
     hipStream_t s = (hipStream_t)stream;
-    // certified Brent paths: trace buffer, per-chunk lists
-    const bool exact_on = c->exact != 0;
+    // certified Brent paths: trace buffer, per-chunk lists (the search only)
+    const bool exact_on = c->exact != 0 && !kw;
     if (exact_on) {
         if ((size_t)n * BT_MAX * sizeof(double) > c->bt_cap) {
             if (c->bt_buf) HIP_TRY(hipFree(c->bt_buf));
@@ -7035,9 +7369,10 @@ int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A
     hipStream_t s2 = c->s2;
     char* const nbws = n_scratch > 0 ? ws_nb(ws, n, n_scratch) : nullptr;
     // demand envelopes of the first-evaluation tariffs prebuilt (k_dc_env)
-    const int dc_pre = (dc && c->dc_buf && c->dc_pre) ? 1 : 0;
+    // (an evaluation's records cover its own size's range: built in k_eval_w)
+    const int dc_pre = (dc && c->dc_buf && c->dc_pre && !kw) ? 1 : 0;
     c->last_paths[6] = dc_pre;
-    const int nb_pre = (n_scratch > 0 && c->nb_pre) ? 1 : 0;
+    const int nb_pre = (n_scratch > 0 && c->nb_pre && !kw) ? 1 : 0;
     const int pre = dc_pre | (nb_pre << 1);     // k_size's view of the two prebuilds
     c->ex_last_nch = exact_on ? nch : 0;
     HIP_TRY(hipEventRecord(c->fork, s));
@@ -7080,7 +7415,9 @@ int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A
         const int64_t nm = (net && !dc && c->nem_hi > i0) ? (c->nem_hi < i1 ? c->nem_hi : i1) : i0;
         const dim3 ygrid_sa((unsigned)((nm - i0 + WAVE / lpa_s - 1) / (WAVE / lpa_s)));
         const dim3 ygrid_sb((unsigned)((i1 - nm + WAVE / lpa_s - 1) / (WAVE / lpa_s)));
-        if (lpa_s == 32 && !dc) {
+        if (kw) {
+            launch_eval(c, T, A, *O, n, i0, i1, nm, dc, n_scratch, nbws, kw, 1, dgen_curve_out{}, 1, s);
+        } else if (lpa_s == 32 && !dc) {
 #if !DGEN_NO2_SIZE
             if (net) {
                 if (nm > i0)
@@ -7320,6 +7657,46 @@ int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A
     }
     HIP_TRY(hipEventRecord(c->join, s2));
     HIP_TRY(hipStreamWaitEvent(s, c->join, 0));
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+
+int32_t dgen_size_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A,
+                         const dgen_outputs* O, int64_t n, void* ws, size_t ws_bytes,
+                         int64_t n_scratch, void* stream) {
+    return size_or_eval(c, T, A, O, nullptr, n, ws, ws_bytes, n_scratch, stream, "dgen_size_agents");
+}
+
+int32_t dgen_eval_agents(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const dgen_outputs* O,
+                         const double* kw, int64_t n, void* ws, size_t ws_bytes, int64_t n_scratch,
+                         void* stream) {
+    if (!kw) { set_err("dgen_eval_agents: null kw"); return DGEN_E_ARG; }
+    return size_or_eval(c, T, A, O, kw, n, ws, ws_bytes, n_scratch, stream, "dgen_eval_agents");
+}
+
+int32_t dgen_objective_curve(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const double* xs,
+                             int32_t K, int64_t n, const dgen_curve_out* out, void* ws, size_t ws_bytes,
+                             int64_t n_scratch, void* stream) {
+    const char* who = "dgen_objective_curve";
+    if (!c || !T || !A || !xs || !out) { set_err("%s: null argument", who); return DGEN_E_ARG; }
+    if (K < 1 || K > 64) { set_err("%s: K must be 1..64 (got %d)", who, (int)K); return DGEN_E_ARG; }
+    if (n <= 0) return DGEN_OK;
+    if (int32_t r = yl_check_args(T, A, who)) return r;
+    if (n >= ((int64_t)1 << 29) || n_scratch < 0 || n_scratch >= ((int64_t)1 << 28)) {
+        set_err("%s: batch too large (n < 2^29, n_scratch < 2^28 per call)", who);
+        return DGEN_E_ARG;
+    }
+    if (!ws || ws_bytes < dgen_workspace_bytes(n, n_scratch)) {
+        set_err("%s: workspace too small (%zu < %zu)", who, ws_bytes, dgen_workspace_bytes(n, n_scratch));
+        return DGEN_E_ARG;
+    }
+    dgen_tables Tk = *T;
+    bool dc = false;
+    if (int32_t r = yl_prepare(c, Tk, n, n_scratch, &dc)) return r;
+    char* const nbws = n_scratch > 0 ? ws_nb(ws, n, n_scratch) : nullptr;
+    const int64_t nm = (n_scratch > 0 && !dc && c->nem_hi > 0) ? (c->nem_hi < n ? c->nem_hi : n) : 0;
+    launch_eval(c, &Tk, A, dgen_outputs{}, n, 0, n, nm, dc, n_scratch, nbws, xs, K, *out, 0, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

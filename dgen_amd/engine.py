@@ -445,9 +445,8 @@ class Engine:
         fields["hourly_f64"] = int(bool(planes) and planes[0].dtype == torch.float64)
         return _lib.Outputs(**fields)
 
-    def size(self, batch: AgentBatch, out: Dict[str, object], c_out: Optional[_lib.Outputs] = None):
-        """Launch the sizing kernels for `batch` on the current stream (async)."""
-        co = c_out if c_out is not None else self.c_outputs(out)
+    def _batch_settings(self, batch: AgentBatch):
+        """The per-batch context settings of a sizing / evaluation call."""
         # no_net / nb_scan were decided against the tables of upload time; after
         # a set_tariffs / set_switches take the forms that are right for any
         # table (the net-billing instantiations, the scan-built split on)
@@ -465,12 +464,68 @@ class Engine:
             _lib.check(self.lib.dgen_set_ts_rows(self.ctx, int(batch.ts_rows[0]), int(batch.ts_rows[1])),
                        "dgen_set_ts_rows")
             self._ts_rows = tuple(batch.ts_rows)
+
+    def size(self, batch: AgentBatch, out: Dict[str, object], c_out: Optional[_lib.Outputs] = None):
+        """Launch the sizing kernels for `batch` on the current stream (async)."""
+        co = c_out if c_out is not None else self.c_outputs(out)
+        self._batch_settings(batch)
         _lib.check(self.lib.dgen_size_agents(self.ctx, ctypes.byref(self.tables),
                                              ctypes.byref(batch.c_agents), ctypes.byref(co),
                                              batch.n, _ptr(batch.workspace),
                                              batch.workspace.numel(), batch.n_scratch,
                                              self.stream_handle()),
                    "dgen_size_agents")
+
+    def evaluate(self, batch: AgentBatch, out: Dict[str, object], kw, c_out: Optional[_lib.Outputs] = None):
+        """size() with the search replaced by one evaluation at kw[j] kW for
+        device row j (dgen_eval_agents; async on the current stream).  kw: a
+        device tensor or host array of batch.n values in the batch's device
+        order (batch.perm maps caller rows to it).  Same outputs and plane
+        forms as size(), with system_kw = x_last = kw and nfev = 1."""
+        torch = _torch()
+        k = self._to_dev(kw, torch.float64).contiguous()
+        if k.dim() != 1 or k.numel() != batch.n:
+            raise ValueError(f"evaluate: kw must hold one size per agent ({batch.n}), got {tuple(k.shape)}")
+        co = c_out if c_out is not None else self.c_outputs(out)
+        self._batch_settings(batch)
+        _lib.check(self.lib.dgen_eval_agents(self.ctx, ctypes.byref(self.tables),
+                                             ctypes.byref(batch.c_agents), ctypes.byref(co), _ptr(k),
+                                             batch.n, _ptr(batch.workspace), batch.workspace.numel(),
+                                             batch.n_scratch, self.stream_handle()),
+                   "dgen_eval_agents")
+        self._keep["_eval_kw"] = k            # alive until the next call (stream order)
+
+    def objective_curve(self, batch: AgentBatch, xs, want=tuple(_lib.CURVE_FIELDS)) -> Dict[str, object]:
+        """The PV-only objective of `batch` at K sizes per agent
+        (dgen_objective_curve; async on the current stream).  xs: [K, n]
+        device tensor or host array, xs[k, j] the k-th size of device row j,
+        1 <= K <= 64; every point is evaluated on its own from the agent's
+        initial tariff.  want: the members to compute (_lib.CURVE_FIELDS).
+        Returns a dict of [K, n] device tensors: npv, payback_raw, first_with,
+        first_without, total_cost (float64), tariff, switched, status (int32);
+        a point that is not finite or not positive has ST_BOUNDS and NaN."""
+        torch = _torch()
+        want = tuple(want)
+        bad = [k for k in want if k not in _lib.CURVE_FIELDS]
+        if bad or not want:
+            raise ValueError(f"objective_curve: want must name members of {_lib.CURVE_FIELDS} (got {want})")
+        x = self._to_dev(xs, torch.float64).contiguous()
+        if x.dim() != 2 or x.shape[1] != batch.n or not 1 <= x.shape[0] <= _lib.CURVE_MAX_POINTS:
+            raise ValueError(f"objective_curve: xs must be [K, {batch.n}] with 1 <= K <= {_lib.CURVE_MAX_POINTS}, "
+                             f"got {tuple(x.shape)}")
+        K = int(x.shape[0])
+        res = {k: torch.empty((K, batch.n), dtype=torch.float64 if k in _lib.CURVE_F64 else torch.int32,
+                              device=self.dev) for k in want}
+        if batch.n == 0:
+            return res
+        self._batch_settings(batch)
+        co = _lib.CurveOut(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(self.lib.dgen_objective_curve(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                                 _ptr(x), K, batch.n, ctypes.byref(co), _ptr(batch.workspace),
+                                                 batch.workspace.numel(), batch.n_scratch, self.stream_handle()),
+                   "dgen_objective_curve")
+        self._keep["_curve_xs"] = x           # alive until the next call (stream order)
+        return res
 
     def hourly_planes(self, batch: AgentBatch, c_out: _lib.Outputs):
         """The hourly planes of `batch`, already sized with the outputs `c_out`

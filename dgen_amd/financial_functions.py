@@ -229,7 +229,7 @@ def device_rows_budget(eng, frac: float = 0.3, grid_metrics: bool = False) -> in
 def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                 hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
-                keep_planes: bool = True):
+                keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -252,7 +252,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     import torch
     try:
         return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
-                                grid_metrics, keep_planes)
+                                grid_metrics, keep_planes, fixed_kw)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -261,15 +261,15 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
             raise
         torch.cuda.empty_cache()
         return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
-                           grid_metrics=grid_metrics, keep_planes=keep_planes)
+                           grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw)
 
 
 def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
-                     grid_metrics: bool = False, keep_planes: bool = True):
+                     grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None):
     n = len(cols["load_kwh"])
     if n <= max_rows:
         return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
-                                grid_metrics, keep_planes)
+                                grid_metrics, keep_planes, fixed_kw)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -284,7 +284,8 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         nw = None if net_weights is None else tuple(np.asarray(w)[lo:hi] for w in net_weights)
         tm: dict = {}
         parts.append(_run_device_once(b, sub, src, tm, nw, hourly_async=True, hourly_device=False,
-                                      grid_metrics=grid_metrics, keep_planes=keep_planes))
+                                      grid_metrics=grid_metrics, keep_planes=keep_planes,
+                                      fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi]))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -317,8 +318,10 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
 
 def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
-                     hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True):
-    """Size the batch in one device call; net_weights = (number_of_adopters, non-adopters) per
+                     hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True,
+                     fixed_kw: Optional[np.ndarray] = None):
+    """Size the batch in one device call (fixed_kw: evaluate caller row i at
+    fixed_kw[i] kW instead, Engine.evaluate); net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
     summed on the device from the planes in place (k_state_hourly, one
     segment, fixed order) instead of a host loop over the agents.
@@ -339,7 +342,11 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     out = eng.alloc_outputs(batch.n, hourly=True, hourly_f64=True)
     torch.cuda.synchronize(eng.dev)
     t1 = time.perf_counter()
-    eng.size(batch, out)
+    if fixed_kw is None:
+        eng.size(batch, out)
+    else:
+        kw = np.asarray(fixed_kw, np.float64)
+        eng.evaluate(batch, out, kw if batch.perm is None else kw[batch.perm])
     net = None
     if net_weights is not None:
         perm = batch.perm if batch.perm is not None else np.arange(batch.n)
@@ -482,9 +489,31 @@ def _yearly_lists(a: np.ndarray, n1: np.ndarray, fmt: str = "list"):
     return list(out)
 
 
+def _fixed_kw_values(df: pd.DataFrame, fixed_kw) -> np.ndarray:
+    """size_frame's fixed_kw as one float64 size per frame row (a column name
+    or an aligned array); ValueError naming the first agent whose size is not
+    finite or not positive."""
+    if isinstance(fixed_kw, str):
+        if fixed_kw not in df:
+            raise KeyError(f"fixed_kw: the frame has no column {fixed_kw!r}")
+        vals = df[fixed_kw].tolist()
+    else:
+        vals = list(np.asarray(fixed_kw).reshape(-1))
+        if len(vals) != len(df):
+            raise ValueError(f"fixed_kw: {len(vals)} values for {len(df)} agents")
+    kw = np.array([_finite_float(v) for v in vals], np.float64)
+    bad = np.nonzero(~(np.isfinite(kw) & (kw > 0.0)))[0]
+    if bad.size:
+        ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
+        k = int(bad[0])
+        raise ValueError(f"agent {ids[k]}: fixed_kw must be finite and positive (got {vals[k]!r}; "
+                         f"{bad.size} such agent(s))")
+    return kw
+
+
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
-               grid_metrics: bool = False):
+               grid_metrics: bool = False, fixed_kw=None):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -514,10 +543,19 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     peak_export_kw_ (float) and peak_import_hour_ / peak_export_hour_ (int
     hour of year, -1 = none) -- digested from the fp64 planes on the device
     (dgen_plane_digest), the same bits in every hourly mode and sub-batching;
-    with hourly="none" the planes then never leave HBM."""
+    with hourly="none" the planes then never leave HBM.  fixed_kw: the name
+    of a frame column, or an array aligned with the frame's rows, of PV sizes
+    in kW: every agent is then evaluated at its value instead of being sized
+    (one calc_system_performance(kw, en_batt=False) from the agent's own
+    tariff, then the PV+battery run at that size; Engine.evaluate) -- same
+    columns, hourly modes, net_weights, grid_metrics and sub-batching; an
+    entry that is not finite or not positive raises ValueError naming the
+    agent before anything is launched.  A frame is sized or evaluated as a
+    whole."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
+    fixed = None if fixed_kw is None else _fixed_kw_values(df, fixed_kw)
     t0 = time.perf_counter()
     src = _source(con)
     src.ensure_frame(df)
@@ -527,7 +565,7 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     dev_t: dict = {}
     o = _run_device(b, cols, src, dev_t, net_weights, hourly_async=hourly in ("lazy", "array", "list"),
                     hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
-                    keep_planes=not (grid_metrics and hourly == "none"))
+                    keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed)
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -606,10 +644,12 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
                hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
-               grid_metrics: bool = False):
+               grid_metrics: bool = False, fixed_kw=None):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
     agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
-    grid_metrics: size_frame's 18 per-agent grid-exchange columns."""
+    grid_metrics: size_frame's 18 per-agent grid-exchange columns.  fixed_kw:
+    size_frame's (a column name or an aligned array: the chunk's agents are
+    evaluated at those sizes instead of being sized)."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -622,7 +662,8 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     # on the device; the reference's running sum in agent order and the
     # kernel's fixed-order tree agree to rounding (parity test: 1e-12 relative)
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
-                           net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics)
+                           net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics,
+                           fixed_kw=fixed_kw)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

@@ -18,7 +18,7 @@ driven to the bracket's top).  A wave-uniform branch (one agent per wave) is
 lowered to a scalar branch with no exec restore, so it cannot occur there.
 
 dgen_amd/build.py runs scan() on the device assembly of every build (the
-same compile, -save-temps): a flagged 32-lane k_size / k_batt_finance
+same compile, -save-temps): a flagged 32-lane k_size / k_eval / k_batt_finance
 instantiation is withdrawn (REMEDY: its batches run one agent per wave, whose
 branches are wave-uniform) and the library rebuilt; a flagged kernel without
 a remedy fails the build.
@@ -53,6 +53,11 @@ REMEDY = {
     "k_batt_finance_wILi32ELb1ELb1ELb0E": "DGEN_NO2_FIN_DC",
     "k_batt_finance_wILi32ELb1ELb0ELb0E": "DGEN_NO2_FIN_DC",
     "k_batt_finance_wILi32ELb1ELb1ELb1E": "DGEN_NO2_FIN_PK",
+    # the evaluation at caller-given sizes (dgen_eval_agents, dgen_objective_curve)
+    "k_eval_wILi32ELb0E": "DGEN_NO2_EVAL",
+    "k_eval_wILi32ELb1ELb1ELb0E": "DGEN_NO2_EVAL_DC",
+    "k_eval_wILi32ELb1ELb0ELb0E": "DGEN_NO2_EVAL_DC",
+    "k_eval_wILi32ELb1ELb1ELb1E": "DGEN_NO2_EVAL_PK",
 }
 
 

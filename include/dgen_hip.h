@@ -733,6 +733,51 @@ typedef struct {            /* each [12][n], month-major: value (m, i) at [m * n
 int32_t dgen_plane_digest(dgen_ctx* ctx, const void* plane, int32_t plane_f64, int64_t n,
                           const dgen_digest_out* out, void* stream);
 
+/* Evaluate a batch at caller-given sizes (additive to ABI 14):
+ * dgen_size_agents with the bounded Brent search replaced by one evaluation of
+ * its objective, calc_system_performance(kw[i], en_batt=False) from the agent's
+ * initial tariff state (tariff0, not switched), then the same PV+battery
+ * forward run at kw[i].  `kw` is [n] doubles on the device, in the batch's row
+ * order.  Outputs as dgen_size_agents writes them with system_kw = x_last =
+ * kw[i] bit for bit and nfev = 1; a size that is not finite or not positive
+ * (0 is not supported: the net-billing split and the demand envelopes
+ * degenerate there) gets DGEN_ST_BOUNDS, nfev 0 and NaN outputs.  Argument
+ * checks, plane forms, the chunk pipeline, the dgen_set_battery / _pipeline /
+ * _hourly_segment / _nb_scan / _dc_records / _ts_rows / _nem_rows settings and
+ * the dgen_kernel_times accounting (the evaluation in the k_size slot) are
+ * dgen_size_agents'; dgen_hourly_planes, dgen_export_plane and
+ * dgen_state_hourly_rows take its outputs as they take a sizing call's.
+ * dgen_set_exact does not apply: there is no search path to certify, nothing
+ * of that machinery is allocated or launched and a following
+ * dgen_exact_count reports 0.  dgen_set_dc_prebuild does not apply either: the
+ * split and the envelopes cover the evaluated size's generation range, not the
+ * bracket's, and are built inside the evaluation (dgen_last_paths out[6] is
+ * 0).  Replaces nothing in the reference (its only way to the objective is the
+ * search, ff:440-447).                                                        */
+int32_t dgen_eval_agents(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                         const dgen_outputs* out, const double* kw, int64_t n, void* workspace,
+                         size_t ws_bytes, int64_t n_scratch, void* stream);
+
+/* The PV-only objective at K sizes per agent (additive to ABI 14).  xs is
+ * [K][n] doubles on the device, point-major (point k of agent i at
+ * xs[k * n + i]), 1 <= K <= 64.  Every point is evaluated on its own from the
+ * agent's initial tariff state, as dgen_eval_agents does, so column k equals a
+ * dgen_eval_agents call at xs[k] bit for bit on the shared members; the rate
+ * switch's stickiness does not carry from one point to the next.  A point that
+ * is not finite or not positive gets DGEN_ST_BOUNDS in `status` and NaN, and
+ * leaves the agent's other points as they are.  Launches the evaluation kernel
+ * alone: no dgen_outputs, no hourly scan, no battery run, no kernel-time
+ * record.  Table and agent-column checks and the workspace are
+ * dgen_size_agents'.  A NULL member is not written.                          */
+typedef struct {            /* each [K][n], point-major; any may be NULL */
+    double  *npv, *payback_raw, *first_with, *first_without, *total_cost;
+    int32_t *tariff, *switched, *status;
+} dgen_curve_out;
+
+int32_t dgen_objective_curve(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                             const double* xs, int32_t K, int64_t n, const dgen_curve_out* out,
+                             void* workspace, size_t ws_bytes, int64_t n_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
