@@ -264,3 +264,145 @@ def at_device_point(o, i: int, opop, j: int, cfg, r, xatol: float, hourly: bool 
     e = opop.eval_at(cfg, j, kw, xl, int(o["tariff_final"][i]), int(o["switched"][i]), hourly=hourly)
     e["nfev"] = int(o["nfev"][i])
     return e
+
+
+# ---------------------------------------------------------------------------
+# GPU <-> oracle comparison of a sized batch (DESIGN.md section 2 tolerances)
+# ---------------------------------------------------------------------------
+def check_sized_against_oracle(o, ref, cols, payback_raw=False):
+    """Every agent of the host outputs `o` (outputs_to_host, hourly planes
+    included) against the oracle results `ref` (Population.run(hourly=True)):
+    status 0 on both sides, the oracle's Brent path (certified paths), the
+    scalars, the five yearly arrays over [:N + 1] and the two hourly planes.
+    payback_raw: also the unrounded payback, 1e-9 relative.  Returns the
+    number of agents that switched rate."""
+    n_switch = 0
+    for i, r in enumerate(ref):
+        assert o["status"][i] == 0 and r["status"] == 0, i
+        # every agent on the oracle's Brent path (certified paths, DESIGN.md section 2)
+        assert same_path(o, i, r), (i, o["nfev"][i], r["nfev"], o["system_kw"][i], r["system_kw"])
+        assert o["nfev"][i] == r["nfev"], (i, o["nfev"][i], r["nfev"])
+        assert o["tariff_final"][i] == r["tariff_final"], i
+        assert o["switched"][i] == r["switched"], i
+        n_switch += int(r["switched"])
+        assert abs(o["system_kw"][i] - r["system_kw"]) <= 1e-9 * max(1.0, r["system_kw"]), i
+        for k in ("npv", "annual_kwh", "first_with", "first_without", "batt_kwh", "batt_kw",
+                  "npv_pv_batt"):
+            assert np.isclose(o[k][i], r[k], rtol=1e-6, atol=1e-6), (i, k, o[k][i], r[k])
+        assert o["payback_period"][i] == r["payback_period"], (i, o["payback_raw"][i], r["payback_raw"])
+        if payback_raw:
+            assert abs(o["payback_raw"][i] - r["payback_raw"]) <= 1e-9 * abs(r["payback_raw"]), \
+                (i, o["payback_raw"][i], r["payback_raw"])
+        N1 = int(cols["econ_life"][i]) + 1
+        for k_o, k_r in (("cash_flow", "cash_flow"), ("cfev_pv", "cf_energy_value_pv_only"),
+                         ("bill_w_pv", "bill_w_pv_only"), ("cfev_batt", "cf_energy_value_pv_batt"),
+                         ("bill_w_batt", "bill_w_pv_batt")):
+            assert np.allclose(o[k_o][i, :N1], r[k_r], rtol=1e-6, atol=1e-5), (i, k_o)
+        for k_o, k_r in (("net_pvonly", "adopter_net_hourly_pvonly"),
+                         ("net_with_batt", "adopter_net_hourly_with_batt")):
+            ref_h = r[k_r]
+            assert np.allclose(o[k_o][i], ref_h, rtol=1e-5, atol=1e-5 * max(1.0, np.abs(ref_h).max())), (i, k_o)
+    return n_switch
+
+
+# ---------------------------------------------------------------------------
+# Edge populations: dgen_amd.synth gives every agent one point of the
+# financing parameter space (life 25, term 20 / 30, ...); these overwrite the
+# financing columns of a small synthetic population with the values where the
+# Cashloan arithmetic branches, and lay the lives out by wave pair.
+# ---------------------------------------------------------------------------
+EDGE_SHORT_LIVES = (1, 2, 3, 6, 7, 8, 16, 25, 31, 32)
+EDGE_LONG_LIVES = (1, 2, 7, 32, 33, 49, 50)
+# device rows 2k, 2k + 1 share a wave when every life is <= 32: these pairs come first
+EDGE_PAIRS = ((1, 32), (32, 1), (32, 32), (1, 1), (7, 8), (25, 2))
+EDGE_VALUES = {
+    "loan_term": (0, 1, 5, 10, 20, 32, 40),
+    "down_payment": (0.0, 0.3, 1.0),
+    "tax_rate": (0.0, 0.2574, 0.45),
+    "real_discount": (0.0, 0.05, 0.15),
+    "inflation": (-0.01, 0.0, 0.025, 0.08),
+    "pv_deg": (0.0, 0.005, 0.05),
+    "itc_frac": (0.0, 0.3, 1.0),
+    "escalator": (-0.03, 0.0, 0.04),
+}
+EDGE_CAPEX_FACTORS = (0.05, 0.3, 1.0)       # payback in year 1, late, never
+
+
+def edge_lives(n, lives, rng):
+    """econ_life per row.  "short": the EDGE_PAIRS first, then pairs of two
+    different EDGE_SHORT_LIVES; "long": EDGE_LONG_LIVES drawn per row (the
+    batch then runs one agent per wave)."""
+    if lives == "long":
+        life = rng.choice(EDGE_LONG_LIVES, n)
+        assert life.max() > 32
+        return life.astype(np.int32)
+    assert lives == "short", lives
+    pairs = list(EDGE_PAIRS)
+    while 2 * len(pairs) < n:
+        a, b = rng.choice(EDGE_SHORT_LIVES, 2, replace=False)
+        pairs.append((int(a), int(b)))
+    assert n >= 2 * len(EDGE_PAIRS)
+    assert sum(a != b for a, b in pairs[:n // 2]) * 4 >= 3 * (n // 2)
+    return np.asarray(pairs, np.int32).reshape(-1)[:n].copy()
+
+
+def edge_population(cfg, n, lives, seed, storage_rows=True):
+    """make_population(cfg, n) at the small table sizes of
+    test_gpu_synthetic._small_pop with the financing columns overwritten from
+    default_rng(seed): EDGE_VALUES per agent, capex and capex_combined scaled
+    by one of EDGE_CAPEX_FACTORS, lives laid out by edge_lives.  storage_rows:
+    every second agent (the odd rows) gets a storage rate-switch candidate --
+    the solar row of another agent of its sector and state class, i.e. of a
+    different utility, where the population has one, else its own -- and the
+    scratch slots are assigned again."""
+    from dgen_amd.columnar import assign_scratch
+    from dgen_amd.synth import make_population
+    pop = make_population(cfg, n, n_res_shapes=64, n_com_shapes=32, n_cf=32, n_counties=16,
+                          n_tariffs=48)
+    rng = np.random.default_rng(seed)
+    c = pop.cols
+    c["econ_life"] = edge_lives(n, lives, rng)
+    for name, values in EDGE_VALUES.items():
+        c[name] = rng.choice(values, n).astype(c[name].dtype)
+    f = rng.choice(EDGE_CAPEX_FACTORS, n)
+    c["capex"] = c["capex"] * f
+    c["capex_combined"] = c["capex_combined"] * f
+    assert (c["loan_term"] < c["econ_life"]).any() and (c["loan_term"] > c["econ_life"]).any()
+    if storage_rows:
+        off, cnt = c["sw_storage_off"].copy(), c["sw_storage_cnt"].copy()
+        has = c["sw_solar_cnt"] > 0
+        for i in range(1, n, 2):
+            same = has & (c["flags"] == c["flags"][i])
+            other = np.unique(c["sw_solar_off"][same & (c["sw_solar_off"] != c["sw_solar_off"][i])])
+            if other.size:
+                off[i], cnt[i] = other[rng.integers(0, other.size)], 1
+            elif has[i]:
+                off[i], cnt[i] = c["sw_solar_off"][i], 1
+        c["sw_storage_off"], c["sw_storage_cnt"] = off, cnt
+    pop.n_scratch = assign_scratch(c, pop.tariffs, pop.switches)
+    return pop
+
+
+def edge_coverage(cols, ref, ref_no_storage=None, slots=True, switch=True, early=True):
+    """The edges an edge population must reach, from the columns and the
+    oracle's results alone (never device output).  slots / switch / early: off
+    for populations that cannot hold the edge (no tariff that needs a scratch
+    slot; no rate-switch row in reach; no payback within the first year)."""
+    n = len(ref)
+    raw = np.array([r["payback_raw"] for r in ref])
+    none = raw >= 1e98               # SSC's 1e99: no year's cumulative flow turns positive
+    assert (~none).sum() * 10 >= n and none.sum() * 10 >= n, (int(none.sum()), n)
+    if early:
+        assert (raw < 1.0).any()
+    life, term = np.asarray(cols["econ_life"]), np.asarray(cols["loan_term"])
+    assert (term == 0).any() and (term > life).any() and (np.asarray(cols["down_payment"]) == 1.0).any()
+    if slots:
+        assert ((np.asarray(cols["pv_deg"]) == 0.0) & (np.asarray(cols["scratch_slot"]) >= 0)).any()
+    assert (life == 1).any() and (life == 32).any()
+    if switch:
+        assert sum(int(r["switched"]) for r in ref) >= 1
+    if ref_no_storage is not None:
+        if switch:                 # a switch made by the search itself, not only by the battery run
+            assert sum(int(r["switched"]) for r in ref_no_storage) >= 1
+        moved = sum(r["npv_pv_batt"] != q["npv_pv_batt"] for r, q in zip(ref, ref_no_storage))
+        assert moved >= 4, moved

@@ -47,29 +47,7 @@ def test_synthetic_population_matches_oracle(engine, cfg, n, long_life):
                                      pop.wholesale)
     cfg_o = orc.make_cfg()
     ref = opop.run(cfg_o, hourly=True)
-    n_switch = 0
-    for i, r in enumerate(ref):
-        assert o["status"][i] == 0 and r["status"] == 0, i
-        # every agent on the oracle's Brent path (certified paths)
-        assert helpers.same_path(o, i, r), (i, o["nfev"][i], r["nfev"], o["system_kw"][i], r["system_kw"])
-        assert o["nfev"][i] == r["nfev"], (i, o["nfev"][i], r["nfev"])
-        assert o["tariff_final"][i] == r["tariff_final"], i
-        assert o["switched"][i] == r["switched"], i
-        n_switch += int(r["switched"])
-        assert abs(o["system_kw"][i] - r["system_kw"]) <= 1e-9 * max(1.0, r["system_kw"]), i
-        for k in ("npv", "annual_kwh", "first_with", "first_without", "batt_kwh", "batt_kw",
-                  "npv_pv_batt"):
-            assert np.isclose(o[k][i], r[k], rtol=1e-6, atol=1e-6), (i, k, o[k][i], r[k])
-        assert o["payback_period"][i] == r["payback_period"], (i, o["payback_raw"][i], r["payback_raw"])
-        N1 = int(pop.cols["econ_life"][i]) + 1
-        for k_o, k_r in (("cash_flow", "cash_flow"), ("cfev_pv", "cf_energy_value_pv_only"),
-                         ("bill_w_pv", "bill_w_pv_only"), ("cfev_batt", "cf_energy_value_pv_batt"),
-                         ("bill_w_batt", "bill_w_pv_batt")):
-            assert np.allclose(o[k_o][i, :N1], r[k_r], rtol=1e-6, atol=1e-5), (i, k_o)
-        for k_o, k_r in (("net_pvonly", "adopter_net_hourly_pvonly"),
-                         ("net_with_batt", "adopter_net_hourly_with_batt")):
-            ref_h = r[k_r]
-            assert np.allclose(o[k_o][i], ref_h, rtol=1e-5, atol=1e-5 * max(1.0, np.abs(ref_h).max())), (i, k_o)
+    n_switch = helpers.check_sized_against_oracle(o, ref, pop.cols)
     if cfg != "ca_res_storage":
         assert n_switch > 0          # the population exercises the DG switch
     if cfg == "com_kwkw":            # kWh/kW tier units on >= 30 % of the agents, all sized
