@@ -121,6 +121,25 @@ class CurveOut(ctypes.Structure):
     _fields_ = [(name, _vp) for name in CURVE_FIELDS]
 
 
+BATT_SUMMARY_F64 = ["pv_kwh", "surplus_kwh", "pv_to_batt_kwh", "pv_to_grid_kwh", "pv_to_load_kwh",
+                    "batt_to_load_kwh", "grid_to_load_kwh", "surplus_mid_kwh", "pv_to_batt_mid_kwh",
+                    "pv_to_grid_mid_kwh", "soc_min", "soc_max", "soc_end"]
+BATT_SUMMARY_I32 = ["hours_charge", "hours_discharge", "hours_soc_bound", "hours_power_bound", "hours_empty",
+                    "hours_discharge_power_bound"]
+BATT_SUMMARY_FIELDS = BATT_SUMMARY_F64 + BATT_SUMMARY_I32
+BATT_SUMMARY_MIDDAY = (11, 15)   # include/dgen_hip.h dgen_batt_summary: the window of a NULL opt
+
+
+class BattSummaryOpt(ctypes.Structure):
+    """dgen_batt_summary_opt: the midday window, hours of day, inclusive."""
+    _fields_ = [("mid_lo", _i32), ("mid_hi", _i32)]
+
+
+class BattSummaryOut(ctypes.Structure):
+    """dgen_batt_summary_out: [12][n] month-major device planes, any may be NULL."""
+    _fields_ = [(name, _vp) for name in BATT_SUMMARY_FIELDS]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -138,7 +157,7 @@ EXPORTED = [
     "dgen_kernel_times", "dgen_last_paths", "dgen_set_dc_prebuild", "dgen_segment_sums", "dgen_max_market_share", "dgen_diffusion",
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
-    "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve",
+    "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
 ]
 
 
@@ -224,6 +243,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_objective_curve.restype = _i32
     L.dgen_objective_curve.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _vp, _i32, _i64,
                                        ctypes.POINTER(CurveOut), _vp, ctypes.c_size_t, _i64, _vp]
+    L.dgen_batt_summary.restype = _i32
+    L.dgen_batt_summary.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
+                                    _i64, ctypes.POINTER(BattSummaryOpt), ctypes.POINTER(BattSummaryOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

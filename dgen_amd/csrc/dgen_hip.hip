@@ -6738,6 +6738,167 @@ k_size_exact(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, const i
         __syncthreads();
     }
 }
+
+// ---------------------------------------------------------------------------
+// Per-agent monthly battery dispatch summary (dgen_batt_summary; the
+// definition is in include/dgen_hip.h): k_hourly_batt's dispatch replayed for a
+// sized batch with nothing stored per hour.  Lane per agent, the year in hour
+// order with the SOC in a register; the month's sums, SOC range and hour counts
+// are written at each month end ([12][n], a wave's 64 agents contiguous).
+// The dispatch is the scan's own device functions (batt_size, sort24_desc,
+// day_target_sorted, batt_hour) on operands formed the same way, so SOC and
+// the grid-to-load flow are the scan's bits; the hour's charge and discharge
+// are formed beside batt_hour from the pre-hour SOC with its clamp
+// expressions (the compiler shares them with the inlined copy).
+// Day pipeline: plain 16-B global loads, 6 of the shape row and 6 of the cf
+// row per lane-day (rows and days are 16-B multiples), the next day's issued
+// ahead of the current day's sort so they land under ~2000 VALU ops; no LDS.
+// Without a bank (battery off, kW* = 0) bank = power = 0: every clamp and the
+// target come out 0 by arithmetic, no branch.  The hour loop is unrolled and
+// every update a select; the only divergence in the day loop is
+// day_target_sorted's own (saturated days bisect).
+// ---------------------------------------------------------------------------
+constexpr int BS_BLOCK = 64;
+struct BsDay {
+    f32x4 s[6];
+    i32x4 c[6];
+};
+__device__ __forceinline__ void bs_day_load(const float* __restrict__ shp, const int32_t* __restrict__ cfp,
+                                            int d, BsDay& r) {
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        r.s[q] = *reinterpret_cast<const f32x4*>(shp + d * 24 + 4 * q);
+        r.c[q] = *reinterpret_cast<const i32x4*>(cfp + d * 24 + 4 * q);
+    }
+}
+struct BsMonth {
+    double pv, sur, p2b, p2g, p2l, b2l, g2l, sur_m, p2b_m, p2g_m, smin, smax, send;
+    int hc, hd, hsb, hpb, he, hdp;
+};
+__device__ __forceinline__ void bs_month_store(const dgen_batt_summary_out& S, int64_t o, const BsMonth& a) {
+    if (S.pv_kwh) S.pv_kwh[o] = a.pv;
+    if (S.surplus_kwh) S.surplus_kwh[o] = a.sur;
+    if (S.pv_to_batt_kwh) S.pv_to_batt_kwh[o] = a.p2b;
+    if (S.pv_to_grid_kwh) S.pv_to_grid_kwh[o] = a.p2g;
+    if (S.pv_to_load_kwh) S.pv_to_load_kwh[o] = a.p2l;
+    if (S.batt_to_load_kwh) S.batt_to_load_kwh[o] = a.b2l;
+    if (S.grid_to_load_kwh) S.grid_to_load_kwh[o] = a.g2l;
+    if (S.surplus_mid_kwh) S.surplus_mid_kwh[o] = a.sur_m;
+    if (S.pv_to_batt_mid_kwh) S.pv_to_batt_mid_kwh[o] = a.p2b_m;
+    if (S.pv_to_grid_mid_kwh) S.pv_to_grid_mid_kwh[o] = a.p2g_m;
+    if (S.soc_min) S.soc_min[o] = a.smin;
+    if (S.soc_max) S.soc_max[o] = a.smax;
+    if (S.soc_end) S.soc_end[o] = a.send;
+    if (S.hours_charge) S.hours_charge[o] = a.hc;
+    if (S.hours_discharge) S.hours_discharge[o] = a.hd;
+    if (S.hours_soc_bound) S.hours_soc_bound[o] = a.hsb;
+    if (S.hours_power_bound) S.hours_power_bound[o] = a.hpb;
+    if (S.hours_empty) S.hours_empty[o] = a.he;
+    if (S.hours_discharge_power_bound) S.hours_discharge_power_bound[o] = a.hdp;
+}
+
+// midmask: bit k set when hour of day k is inside the midday window
+__global__ void __launch_bounds__(BS_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_batt_summary(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t n, int batt_on,
+               uint32_t midmask, dgen_batt_summary_out S) {
+    const int64_t i = (int64_t)blockIdx.x * BS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int status = O.status[i];
+    if (status & (DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_YEARS)) {   // the scan skips these agents
+        const BsMonth z = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0};
+        for (int m = 0; m < 12; m++) bs_month_store(S, (int64_t)m * n + i, z);
+        return;
+    }
+    // the scan's prologue (k_hourly_batt), operation for operation
+    const bool is_res = (A.flags[i] & 1) != 0;
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double kwh = A.load_kwh[i];
+    const double ls = kwh / T.shape_sum[lr];
+    const bool unsized = (status & DGEN_ST_UNIT) != 0;
+    const double kw_star = unsized ? 0.0 : O.system_kw[i];
+    const double cs6 = (((kw_star * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    double desired_kwh = kw_star / 0.8, desired_kw = desired_kwh / 2.0;
+    double bank = 0.0, power = 0.0;
+    if (batt_on) batt_size(desired_kw, desired_kwh, is_res ? 240.0 : 500.0, cfg, &bank, &power);
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    // the counts' thresholds (include/dgen_hip.h)
+    const double soc_hi = cfg.batt_max_soc - 1e-9, soc_lo = cfg.batt_min_soc + 1e-9;
+    const double pw_hi = power + 1e-6, pw_dis = power * (1.0 - 1e-9);
+    const bool has_pw = power > 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    double soc = cfg.batt_init_soc;
+    BsDay cur, nxt;
+    bs_day_load(shp, cfp, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        BsMonth a = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY, 0.0, 0, 0, 0, 0, 0, 0};
+        double mfloor = 0.0;
+        for (int d = c_month_start_day[m]; d < c_month_start_day[m + 1]; d++) {
+            // the next day's rows, ahead of this day's sort (December 31 loads itself again)
+            bs_day_load(shp, cfp, d < 364 ? d + 1 : 364, nxt);
+            double dv[24];
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++)
+                dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+            sort24_desc(dv);
+            const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+            double target = day_target_sorted(dv, power, avail0);
+            {   // dgen_cfg.batt_month_floor: the month's target never falls
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            // the hour loop forms load and PV again from the raw day (opaque: the
+            // compiler would otherwise keep the 48 fp64 values of the sort's
+            // inputs live across it, 96 registers)
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                const double ld = (double)opaque_f(cur.s[hh >> 2][hh & 3]) * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                const double nn = ld - pv;
+                const double soc0 = soc;
+                const HourStep hs = batt_hour(nn, pv, target, power, bank, soc, cfg, inv_eta_in, in_per_bank,
+                                              out_per_bank);
+                // the hour's flows: batt_hour's clamps at the pre-hour SOC
+                const bool chg = nn < 0.0;
+                const double room = fmax((cfg.batt_max_soc - soc0) * bank * inv_eta_in, 0.0);
+                const double avail = fmax((soc0 - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+                const double cc = chg ? fmin(fmin(-nn, power), room) : 0.0;
+                const double dd = chg ? 0.0 : fmin(fmin(fmax(nn - target, 0.0), power), avail);
+                const double sur = fmax(-nn, 0.0);
+                const double p2g = sur - cc;
+                const bool mid = ((midmask >> hh) & 1u) != 0;      // wave-uniform
+                a.pv += pv;
+                a.sur += sur;
+                a.p2b += cc;
+                a.p2g += p2g;
+                a.p2l += fmin(ld, pv);
+                a.b2l += dd;
+                a.g2l += hs.g2l;
+                a.sur_m += mid ? sur : 0.0;
+                a.p2b_m += mid ? cc : 0.0;
+                a.p2g_m += mid ? p2g : 0.0;
+                a.smin = fmin(a.smin, soc);
+                a.smax = fmax(a.smax, soc);
+                const bool full = soc >= soc_hi;
+                a.hc += cc > 0.0;
+                a.hd += dd > 0.0;
+                a.hsb += sur > 1e-6 && full;
+                a.hpb += sur > pw_hi && soc < soc_hi;
+                a.he += nn > 1e-6 && soc <= soc_lo;
+                a.hdp += dd > pw_dis && has_pw;
+            }
+            cur = nxt;
+        }
+        a.send = soc;
+        bs_month_store(S, (int64_t)m * n + i, a);
+    }
+}
 #endif  // !DGEN_TU_SEARCH
 
 }  // namespace
@@ -8214,6 +8375,51 @@ int32_t dgen_plane_digest(dgen_ctx* c, const void* plane, int32_t plane_f64, int
     else
         hipLaunchKernelGGL((k_plane_digest<float>), grid, dim3(DG_BLOCK), 0, (hipStream_t)stream,
                            (const float*)plane, n, *out);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_batt_summary(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const dgen_outputs* O,
+                          int64_t n, const dgen_batt_summary_opt* opt, const dgen_batt_summary_out* out,
+                          void* stream) {
+    if (!c || !T || !A || !O || !out || n < 0) {
+        set_err("dgen_batt_summary: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand)) {
+        set_err("dgen_batt_summary: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    if (!A->load_row || !A->cf_row || !A->load_kwh || !A->flags) {
+        set_err("dgen_batt_summary: missing agent column (load_row, cf_row, load_kwh, flags)");
+        return DGEN_E_ARG;
+    }
+    if (!O->system_kw || !O->status) {
+        set_err("dgen_batt_summary: missing output column (system_kw, status of the sizing call)");
+        return DGEN_E_ARG;
+    }
+    if (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1) {
+        set_err("dgen_batt_summary: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not summarised: the daily plan under constant efficiencies only");
+        return DGEN_E_ARG;
+    }
+    const int lo = opt ? opt->mid_lo : 11, hi = opt ? opt->mid_hi : 15;
+    if (lo < 0 || hi > 23 || lo > hi) {
+        set_err("dgen_batt_summary: midday window [%d, %d] must satisfy 0 <= mid_lo <= mid_hi <= 23", lo, hi);
+        return DGEN_E_ARG;
+    }
+    const int64_t blocks = (n + BS_BLOCK - 1) / BS_BLOCK;
+    if (blocks > 0x7fffffff) {
+        set_err("dgen_batt_summary: n = %lld exceeds the launch grid", (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    uint32_t midmask = 0;
+    for (int k = lo; k <= hi; k++) midmask |= 1u << k;
+    HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_batt_summary, dim3((unsigned)blocks), dim3(BS_BLOCK), 0, (hipStream_t)stream, *T, *A, *O,
+                       c->cfg, n, c->battery, midmask, *out);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

@@ -691,6 +691,39 @@ class Engine:
                                               ctypes.byref(co), self.stream_handle()), "dgen_plane_digest")
         return res
 
+    def batt_summary(self, batch: AgentBatch, outputs, want=None,
+                     midday=_lib.BATT_SUMMARY_MIDDAY) -> Dict[str, object]:
+        """Per-agent monthly battery dispatch summary of `batch`, already sized
+        or evaluated into `outputs` (the alloc_outputs dict, or its c_outputs;
+        system_kw and status are read, no plane is needed) --
+        dgen_batt_summary, async on the current stream: the scan's dispatch
+        replayed with the SOC and the hour's flows reduced per calendar month.
+        want: the members to compute (default all of _lib.BATT_SUMMARY_FIELDS);
+        midday: the (lo, hi) hours of day, inclusive, of the *_mid_kwh sums.
+        Returns a dict of [12, n] device tensors, month-major, in the batch's
+        device order: the kWh and SOC members float64, the hour counts int32
+        (the definitions are in include/dgen_hip.h)."""
+        torch = _torch()
+        want = tuple(_lib.BATT_SUMMARY_FIELDS if want is None else want)
+        bad = [k for k in want if k not in _lib.BATT_SUMMARY_FIELDS]
+        if bad or not want:
+            raise ValueError(f"batt_summary: want must name members of {_lib.BATT_SUMMARY_FIELDS} (got {want})")
+        lo, hi = (int(v) for v in midday)
+        if not 0 <= lo <= hi <= 23:
+            raise ValueError(f"batt_summary: midday must be 0 <= lo <= hi <= 23 (got {tuple(midday)})")
+        co = outputs if isinstance(outputs, _lib.Outputs) else self.c_outputs(outputs)
+        n = batch.n
+        res = {k: torch.empty((12, n), dtype=torch.float64 if k in _lib.BATT_SUMMARY_F64 else torch.int32,
+                              device=self.dev) for k in want}
+        if n == 0:
+            return res
+        so = _lib.BattSummaryOut(**{k: _ptr(v) for k, v in res.items()})
+        opt = _lib.BattSummaryOpt(lo, hi)
+        _lib.check(self.lib.dgen_batt_summary(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                              ctypes.byref(co), n, ctypes.byref(opt), ctypes.byref(so),
+                                              self.stream_handle()), "dgen_batt_summary")
+        return res
+
     def brent_selftest(self, lo, hi, xatol, c2, x0, c1, maxn=64):
         torch = _torch()
         f = lambda v: self._to_dev(np.asarray(v, dtype=np.float64), torch.float64)

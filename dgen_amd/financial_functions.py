@@ -229,7 +229,7 @@ def device_rows_budget(eng, frac: float = 0.3, grid_metrics: bool = False) -> in
 def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                 hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
-                keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None):
+                keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -244,7 +244,9 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     sub-batch's planes in HBM would undo the bound).  grid_metrics: each
     sub-batch also digests its planes on the device (grid_metrics.COLUMNS,
     per-agent values: the bits of one call); keep_planes False: the planes
-    are released after that and never downloaded (o[plane] is None)."""
+    are released after that and never downloaded (o[plane] is None).
+    batt_metrics: each sub-batch also summarises its battery dispatch on the
+    device (batt_metrics.COLUMNS, per-agent values: the bits of one call)."""
     n = len(cols["load_kwh"])
     if max_rows is None:
         max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics)
@@ -252,7 +254,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     import torch
     try:
         return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
-                                grid_metrics, keep_planes, fixed_kw)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -261,15 +263,17 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
             raise
         torch.cuda.empty_cache()
         return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
-                           grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw)
+                           grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw,
+                           batt_metrics=batt_metrics)
 
 
 def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
-                     grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None):
+                     grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None,
+                     batt_metrics: bool = False):
     n = len(cols["load_kwh"])
     if n <= max_rows:
         return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
-                                grid_metrics, keep_planes, fixed_kw)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -285,7 +289,8 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         tm: dict = {}
         parts.append(_run_device_once(b, sub, src, tm, nw, hourly_async=True, hourly_device=False,
                                       grid_metrics=grid_metrics, keep_planes=keep_planes,
-                                      fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi]))
+                                      fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi],
+                                      batt_metrics=batt_metrics))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -296,6 +301,10 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
     if grid_metrics:
         from .grid_metrics import COLUMNS
         for name in COLUMNS:
+            o[name] = np.concatenate([p[name] for p in parts])
+    if batt_metrics:
+        from .batt_metrics import COLUMNS as BATT_COLUMNS
+        for name in BATT_COLUMNS:
             o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
         if not keep_planes:
@@ -319,7 +328,7 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
 def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                      hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True,
-                     fixed_kw: Optional[np.ndarray] = None):
+                     fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False):
     """Size the batch in one device call (fixed_kw: evaluate caller row i at
     fixed_kw[i] kW instead, Engine.evaluate); net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
@@ -329,7 +338,9 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     (downloading on a background thread), everything else at once.
     grid_metrics: o also holds grid_metrics.COLUMNS, the annual grid-exchange
     digest of the three planes taken on the device (caller order); keep_planes
-    False then releases the planes without a download (o[plane] is None)."""
+    False then releases the planes without a download (o[plane] is None).
+    batt_metrics: o also holds batt_metrics.COLUMNS, the annual battery
+    dispatch summary of the sized batch (Engine.batt_summary, caller order)."""
     import time
     import torch
     from .attachment import state_hourly
@@ -355,6 +366,10 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         pv = out["net_pvonly"]
         net = state_hourly(eng, (out["baseline"], pv, pv), (na, torch.zeros_like(na), nn), None,
                            [0, batch.n])[0] * 1000.0
+    bm = None
+    if batt_metrics:
+        from .batt_metrics import annual_columns as batt_columns
+        bm = batt_columns(eng, batch, out)
     gm = None
     if grid_metrics:
         from .grid_metrics import annual_columns
@@ -380,6 +395,8 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         o["net_sum_kw"] = net.cpu().numpy()
     if gm is not None:           # after the unsized rows' NaNs: their no-system planes digest like any other
         o.update(gm)
+    if bm is not None:
+        o.update(bm)
     if timing is not None:
         timing.update(upload_s=t1 - t0, device_s=t2 - t1, download_s=time.perf_counter() - t2)
     return o
@@ -513,7 +530,7 @@ def _fixed_kw_values(df: pd.DataFrame, fixed_kw) -> np.ndarray:
 
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
-               grid_metrics: bool = False, fixed_kw=None):
+               grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -551,7 +568,14 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     columns, hourly modes, net_weights, grid_metrics and sub-batching; an
     entry that is not finite or not positive raises ValueError naming the
     agent before anything is launched.  A frame is sized or evaluated as a
-    whole."""
+    whole.  batt_metrics: the frame gains the scalar columns
+    batt_metrics.COLUMNS (prefix batt_diag_) -- the year's PV surplus and its
+    split (battery, grid), the load's supply (PV, battery, grid), the midday
+    sums, the SOC range, the hours the bank charged, discharged, sat full,
+    empty or power-limited, and capture_mid_frac, equiv_full_cycles,
+    self_sufficiency_frac -- from a replay of the dispatch on the device
+    (dgen_batt_summary) after each sub-batch's sizing or evaluation; it reads
+    no plane, so the columns are the same bits in every hourly mode."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
@@ -565,7 +589,8 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     dev_t: dict = {}
     o = _run_device(b, cols, src, dev_t, net_weights, hourly_async=hourly in ("lazy", "array", "list"),
                     hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
-                    keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed)
+                    keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed,
+                    batt_metrics=batt_metrics)
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -634,6 +659,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
         from .grid_metrics import COLUMNS
         for name in COLUMNS:
             out[name] = o[name]
+    if batt_metrics:
+        from .batt_metrics import COLUMNS as BATT_COLUMNS
+        for name in BATT_COLUMNS:
+            out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:
         # download_wait_s: time the frame assembly waited for the hourly planes
@@ -644,12 +673,13 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
                hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
-               grid_metrics: bool = False, fixed_kw=None):
+               grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
     agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
     grid_metrics: size_frame's 18 per-agent grid-exchange columns.  fixed_kw:
     size_frame's (a column name or an aligned array: the chunk's agents are
-    evaluated at those sizes instead of being sized)."""
+    evaluated at those sizes instead of being sized).  batt_metrics:
+    size_frame's per-agent battery dispatch columns (batt_diag_*)."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -663,7 +693,7 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     # kernel's fixed-order tree agree to rounding (parity test: 1e-12 relative)
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
                            net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics,
-                           fixed_kw=fixed_kw)
+                           fixed_kw=fixed_kw, batt_metrics=batt_metrics)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

@@ -778,6 +778,81 @@ int32_t dgen_objective_curve(dgen_ctx* ctx, const dgen_tables* tables, const dge
                              const double* xs, int32_t K, int64_t n, const dgen_curve_out* out,
                              void* workspace, size_t ws_bytes, int64_t n_scratch, void* stream);
 
+/* Per-agent monthly battery dispatch summary (additive to ABI 14): a replay of
+ * the hourly scan's peak-shaving dispatch for a batch dgen_size_agents or
+ * dgen_eval_agents already sized (`out`: its system_kw and status are read),
+ * as dgen_hourly_planes replays it, but no plane is stored: the state of charge
+ * and the hour's flows are reduced per calendar month.  One lane per agent, the
+ * year in hour order (SOC carries from month to month).  Per agent i:
+ *   ls  = load_kwh / shape_sum[load_row]
+ *   kW* = system_kw (0 for a DGEN_ST_UNIT agent, as in the scan)
+ *   cs6 = (((kW* x 1000) x 0.96) / 1000) / 1e6
+ *   bank, power = battery_model_sizing(kW* / 0.8 / 2, kW* / 0.8, 240 V
+ *                 residential | 500 V) as the scan sizes it; 0, 0 after
+ *                 dgen_set_battery(0) or for a bank that is not positive
+ *   soc = batt_init_soc
+ * and for every hour h of the non-leap year, in order:
+ *   ld = (double)shape[h] x ls;  pv = (double)cf[h] x cs6;  nn = ld - pv
+ *   at h % 24 == 0: target = the day's peak-shaving target (the scan's plan
+ *       over the day's max(nn, 0) with the energy available at this SOC,
+ *       raised to the month's largest earlier target with batt_month_floor)
+ *   room  = max((batt_max_soc - soc) x bank / batt_eta_in, 0)
+ *   avail = max((soc - batt_min_soc) x bank x batt_eta_out, 0)
+ *   sur = max(-nn, 0)
+ *   cc  = min(min(-nn, power), room)                   if nn < 0, else 0
+ *   dd  = min(min(max(nn - target, 0), power), avail)  if nn >= 0, else 0
+ *   soc, g2l = the scan's hour (soc += cc x eta_in / bank or -= dd / (eta_out
+ *       x bank); g2l = 0 charging, nn - dd otherwise): the same device
+ *       function, so g2l is the with-battery plane's value bit for bit
+ * Members, over the hours of month m in hour order (fp64 sequential sums):
+ *   pv_kwh            sum pv
+ *   surplus_kwh       sum sur
+ *   pv_to_batt_kwh    sum cc
+ *   pv_to_grid_kwh    sum (sur - cc)
+ *   pv_to_load_kwh    sum min(ld, pv)
+ *   batt_to_load_kwh  sum dd
+ *   grid_to_load_kwh  sum g2l
+ *   surplus_mid_kwh, pv_to_batt_mid_kwh, pv_to_grid_mid_kwh
+ *                     the same three sums over the hours with
+ *                     mid_lo <= h % 24 <= mid_hi (default 11, 15)
+ *   soc_min, soc_max  min / max of the end-of-hour SOC (a fraction of the bank)
+ *   soc_end           the SOC after the month's last hour
+ *   hours_charge, hours_discharge    #(cc > 0), #(dd > 0)
+ *   hours_soc_bound   #(sur > 1e-6 and soc >= batt_max_soc - 1e-9)
+ *   hours_power_bound #(sur > power + 1e-6 and soc < batt_max_soc - 1e-9)
+ *   hours_empty       #(nn > 1e-6 and soc <= batt_min_soc + 1e-9)
+ *   hours_discharge_power_bound   #(dd > power x (1 - 1e-9) and power > 0)
+ * with soc the end-of-hour value in the four counts; 1e-6 (kW) and 1e-9 (SOC)
+ * are part of the definition, not tolerances.  Peak shaving never discharges
+ * to the grid (the battery's flow is capped by the hour's net load), so there
+ * is no battery-to-grid member, and pv_to_load + batt_to_load + grid_to_load
+ * is the month's load.  An agent flagged DGEN_ST_BOUNDS, _TARIFF or _YEARS
+ * gets 0 in every member.  Without a bank every flow is 0, the SOC members are
+ * batt_init_soc and grid_to_load is sum max(nn, 0).  Each member is
+ * month-major [12][n] (value (m, i) at [m * n + i]: the k = 12 plane-major
+ * planes dgen_segment_sums takes); a NULL member is not written.  No atomics
+ * and no cross-lane traffic: run-to-run identical.  Table and agent-column
+ * checks are dgen_hourly_planes'; no workspace.  The daily plan under the
+ * constant efficiencies only: batt_update_hours == 1 or batt_loss_model == 1
+ * returns DGEN_E_ARG, as does a window with mid_lo > mid_hi or outside 0..23.
+ * The reference's counterpart is batt_dispatch_helpers.dispatch_export_diags,
+ * one agent at a time from PySAM's hourly arrays: its soc_bound_all and
+ * power_bound_all are the two charge-side counts, with the explicit 1e-9 band
+ * on the SOC fraction in place of its exact >= 95.0.                        */
+typedef struct { int32_t mid_lo, mid_hi; } dgen_batt_summary_opt;   /* NULL: 11, 15 */
+
+typedef struct {            /* each [12][n], month-major; any may be NULL */
+    double  *pv_kwh, *surplus_kwh, *pv_to_batt_kwh, *pv_to_grid_kwh, *pv_to_load_kwh,
+            *batt_to_load_kwh, *grid_to_load_kwh, *surplus_mid_kwh, *pv_to_batt_mid_kwh,
+            *pv_to_grid_mid_kwh, *soc_min, *soc_max, *soc_end;
+    int32_t *hours_charge, *hours_discharge, *hours_soc_bound, *hours_power_bound, *hours_empty,
+            *hours_discharge_power_bound;
+} dgen_batt_summary_out;
+
+int32_t dgen_batt_summary(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                          const dgen_outputs* out, int64_t n, const dgen_batt_summary_opt* opt,
+                          const dgen_batt_summary_out* summary, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
