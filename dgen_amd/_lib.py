@@ -140,6 +140,20 @@ class BattSummaryOut(ctypes.Structure):
     _fields_ = [(name, _vp) for name in BATT_SUMMARY_FIELDS]
 
 
+BILL_FIELDS = ["energy_charge", "export_credit", "fixed_charge", "demand_flat", "demand_tou", "total", "carry",
+               "import_kwh", "export_kwh", "billed_kwh", "peak_kw"]
+
+
+class BillOpt(ctypes.Structure):
+    """dgen_bill_opt: battery = 1 bills the scan's peak-shaving dispatch at the given kW."""
+    _fields_ = [("battery", _i32), ("pad", _i32)]
+
+
+class BillOut(ctypes.Structure):
+    """dgen_bill_out: [12][n] month-major float64 device planes (any may be NULL) and status [n] int32."""
+    _fields_ = [(name, _vp) for name in BILL_FIELDS] + [("status", _vp)]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -158,6 +172,7 @@ EXPORTED = [
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
+    "dgen_bill_months",
 ]
 
 
@@ -246,6 +261,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_batt_summary.restype = _i32
     L.dgen_batt_summary.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
                                     _i64, ctypes.POINTER(BattSummaryOpt), ctypes.POINTER(BattSummaryOut), _vp]
+    L.dgen_bill_months.restype = _i32
+    L.dgen_bill_months.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _vp, _vp, _i64,
+                                   ctypes.POINTER(BillOpt), ctypes.POINTER(BillOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

@@ -6899,6 +6899,328 @@ k_batt_summary(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64
         bs_month_store(S, (int64_t)m * n + i, a);
     }
 }
+
+// ---------------------------------------------------------------------------
+// Year-1 monthly bill breakdown (dgen_bill_months; the definition is in
+// include/dgen_hip.h): the oracle's bin_year / year_bill / year_demand at
+// degradation and escalation factor 1, month by month, for one agent per lane
+// at the caller's kW under the caller's tariff.  The year in hour order, as
+// k_batt_summary walks it (the same day-ahead 16-B row loads; BATT: the same
+// dispatch through the scan's own device functions, its system output
+// pv + f as k_hourly_batt stores it).
+// LDS, [plane][period][lane] doubles (a wave's 64 lanes contiguous: conflict-
+// free ds_read_b64): the month's five (month, period) bins -- net, load,
+// generation, import, export value -- the NEM kWh credit bank per period
+// (it lives across months) and the month's TOU demand peaks; the current
+// period's bins and the current demand period's peak stay in registers until
+// the period changes (the scan's trick).  The day's period rows (energy and
+// demand schedule, 24 B each) are loaded a day ahead with the profile rows.
+// A lane without a demand record reads its energy schedule masked to period 0
+// and tracks a peak nobody bills, so the hour loop has no lane-dependent
+// branch but the two period changes.  TS sell rates: the wave's lanes load
+// the hour quad after the current one (a wave-uniform branch: waves without
+// a TS lane issue nothing; a lane that does not bill TS re-reads one valid
+// double).  The month-end bill is plain per-lane loops over P and T with the
+// tariff read from global memory, twelve times per agent.
+// ---------------------------------------------------------------------------
+constexpr int BM_BLOCK = 64;
+constexpr int BM_PLANES = 6;      // net, load, generation, import, export value, credit bank
+struct BmDay {
+    f32x4 s[6];
+    i32x4 c[6];
+    uint64_t e[3], q[3];          // the day's energy / demand period rows
+};
+__device__ __forceinline__ void bm_day_load(const float* __restrict__ shp, const int32_t* __restrict__ cfp,
+                                            const char* esch, const char* dsch, int d, int m, BmDay& r) {
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        r.s[q] = *reinterpret_cast<const f32x4*>(shp + d * 24 + 4 * q);
+        r.c[q] = *reinterpret_cast<const i32x4*>(cfp + d * 24 + 4 * q);
+    }
+    // wkend[12][24] follows wkday[12][24] in dgen_tariff and in dgen_demand
+    const int off = ((d % 7) >= 5 ? 288 : 0) + 24 * m;
+    const uint64_t* a = reinterpret_cast<const uint64_t*>(esch + off);
+    const uint64_t* b = reinterpret_cast<const uint64_t*>(dsch + off);
+    r.e[0] = a[0]; r.e[1] = a[1]; r.e[2] = a[2];
+    r.q[0] = b[0]; r.q[1] = b[1]; r.q[2] = b[2];
+}
+struct BmMonth {
+    double ec, cr, fixed, dflat, dtou, total, carry, imp, exk, billed, peak;
+};
+__device__ __forceinline__ void bm_month_store(const dgen_bill_out& S, int64_t o, const BmMonth& a) {
+    if (S.energy_charge) S.energy_charge[o] = a.ec;
+    if (S.export_credit) S.export_credit[o] = a.cr;
+    if (S.fixed_charge) S.fixed_charge[o] = a.fixed;
+    if (S.demand_flat) S.demand_flat[o] = a.dflat;
+    if (S.demand_tou) S.demand_tou[o] = a.dtou;
+    if (S.total) S.total[o] = a.total;
+    if (S.carry) S.carry[o] = a.carry;
+    if (S.import_kwh) S.import_kwh[o] = a.imp;
+    if (S.export_kwh) S.export_kwh[o] = a.exk;
+    if (S.billed_kwh) S.billed_kwh[o] = a.billed;
+    if (S.peak_kw) S.peak_kw[o] = a.peak;
+}
+__device__ __forceinline__ void bm_flag(const dgen_bill_out& S, int64_t n, int64_t i, int status) {
+    const double q = __builtin_nan("");
+    const BmMonth z = {q, q, q, q, q, q, q, q, q, q, q};
+    for (int m = 0; m < 12; m++) bm_month_store(S, (int64_t)m * n + i, z);
+    S.status[i] = status;
+}
+
+template <bool BATT>
+__global__ void __launch_bounds__(BM_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_bill_months(dgen_tables T, dgen_agents A, dgen_cfg cfg, const double* __restrict__ kwv,
+              const int32_t* __restrict__ tix, int64_t n, int dc_nq, dgen_bill_out S) {
+    const int64_t i = (int64_t)blockIdx.x * BM_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int PH = lds_half(T.max_periods);
+    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BM_BLOCK]
+    double* const dcl = lds + (size_t)BM_PLANES * PH * BM_BLOCK;   // TOU demand peaks [dc_nq][lane]
+    const double kw = kwv[i];
+    const int ti = tix[i];
+    int status = 0;
+    if (!(kw >= 0.0) || isinf(kw)) status |= DGEN_ST_BOUNDS;
+    if (ti < 0 || ti >= T.n_tariffs) status |= DGEN_ST_TARIFF;
+    else {
+        const dgen_tariff& t0 = T.tariffs[ti];
+        status |= t0.flags;
+        // a table whose max_periods does not cover the tariff is malformed
+        if (t0.P < 1 || t0.P > PH || t0.T < 1 || t0.T > MAXT) status |= DGEN_ST_TARIFF;
+    }
+    if (status) {
+        bm_flag(S, n, i, status);
+        return;
+    }
+    const dgen_tariff& t = T.tariffs[ti];
+    const int P = t.P, NT = t.T, mo = t.mo;
+    const dgen_demand* const dem = tariff_demand(T, cfg, t);
+    const uint8_t aflags = A.flags[i];
+    const bool is_res = (aflags & 1) != 0;
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double kwh = A.load_kwh[i];
+    const double ls = kwh / T.shape_sum[lr];
+    const double cs6 = (((kw * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    // TS sell rate (mo 2, not CA, a wholesale row): ts[h] = (double)(float)(wholesale[h] x price_mult)
+    const int wr = (A.wholesale_row && A.price_mult) ? A.wholesale_row[i] : -1;
+    const bool ts_on = mo == 2 && (aflags & 2) == 0 && wr >= 0 && T.wholesale != nullptr;
+    const bool wave_ts = __ballot(ts_on) != 0;
+    const double* __restrict__ tsp = ts_on ? T.wholesale + (int64_t)wr * NH : T.shape_sum + lr;
+    const int tstride = ts_on ? 1 : 0;
+    const double ts_mult = ts_on ? A.price_mult[i] : 1.0;
+    const char* const esch = reinterpret_cast<const char*>(t.wkday);
+    const char* const dsch = dem ? reinterpret_cast<const char*>(dem->wkday) : esch;
+    const uint32_t dmask = dem ? 0xffu : 0u;
+
+    double bank = 0.0, power = 0.0;
+    if constexpr (BATT) {
+        const double desired_kwh = kw / 0.8, desired_kw = desired_kwh / 2.0;
+        batt_size(desired_kw, desired_kwh, is_res ? 240.0 : 500.0, cfg, &bank, &power);
+    }
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    double soc = cfg.batt_init_soc;
+    (void)is_res; (void)inv_eta_in; (void)in_per_bank; (void)out_per_bank; (void)mfl;
+
+    for (int p = 0; p < P; p++) lds[(5 * PH + p) * BM_BLOCK] = 0.0;      // the NEM credit bank
+    double carry = 0.0;                                                  // the dollar carry (mo 1, 3)
+    double tq[4] = {0.0, 0.0, 0.0, 0.0}, tn[4] = {0.0, 0.0, 0.0, 0.0};   // TS: this hour quad's rates, the next's
+    if (wave_ts) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) tq[j] = tsp[j * tstride];
+    }
+    BmDay cur, nxt;
+    bm_day_load(shp, cfp, esch, dsch, 0, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        for (int p = 0; p < P; p++) {
+#pragma unroll
+            for (int b = 0; b < 5; b++) lds[(b * PH + p) * BM_BLOCK] = 0.0;
+        }
+        for (int q = 0; q < dc_nq; q++) dcl[q * BM_BLOCK] = 0.0;
+        int bcur = 0, dq = 0;
+        double b_net = 0.0, b_ld = 0.0, b_gen = 0.0, b_imp = 0.0, b_exv = 0.0, dacc = 0.0;
+        double peak = 0.0, exk = 0.0, mfloor = 0.0;
+        (void)mfloor;
+        const int d_end = c_month_start_day[m + 1];
+        for (int d = c_month_start_day[m]; d < d_end; d++) {
+            {   // the next day's rows (December 31 loads itself again)
+                const int dn = d < 364 ? d + 1 : 364;
+                bm_day_load(shp, cfp, esch, dsch, dn, dn < d_end ? m : m + 1, nxt);
+            }
+            double target = 0.0;
+            if constexpr (BATT) {
+                double dv[24];
+#pragma unroll
+                for (int hh = 0; hh < 24; hh++)
+                    dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+                sort24_desc(dv);
+                const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+                target = day_target_sorted(dv, power, avail0);
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+            const int h0 = d * 24;
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                if ((hh & 3) == 0 && wave_ts) {        // wave-uniform
+                    const int hn = h0 + hh + 4 <= NH - 4 ? h0 + hh + 4 : NH - 4;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) tn[j] = tsp[(hn + j) * tstride];
+                }
+                const double ld = (double)opaque_f(cur.s[hh >> 2][hh & 3]) * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                double g = pv;
+                if constexpr (BATT) {
+                    const HourStep hs = batt_hour(ld - pv, pv, target, power, bank, soc, cfg, inv_eta_in,
+                                                  in_per_bank, out_per_bank);
+                    g = hs.sys;
+                }
+                const double dd = ld - g;
+                int p = (int)((cur.e[hh >> 3] >> (8 * (hh & 7))) & 0xffu);
+                p = p < P ? p : P - 1;                  // a schedule beyond P: never past the lane's bins
+                if (p != bcur) {
+                    lds[(0 * PH + bcur) * BM_BLOCK] = b_net;
+                    lds[(1 * PH + bcur) * BM_BLOCK] = b_ld;
+                    lds[(2 * PH + bcur) * BM_BLOCK] = b_gen;
+                    lds[(3 * PH + bcur) * BM_BLOCK] = b_imp;
+                    lds[(4 * PH + bcur) * BM_BLOCK] = b_exv;
+                    bcur = p;
+                    b_net = lds[(0 * PH + p) * BM_BLOCK];
+                    b_ld = lds[(1 * PH + p) * BM_BLOCK];
+                    b_gen = lds[(2 * PH + p) * BM_BLOCK];
+                    b_imp = lds[(3 * PH + p) * BM_BLOCK];
+                    b_exv = lds[(4 * PH + p) * BM_BLOCK];
+                }
+                int q = (int)((uint32_t)(cur.q[hh >> 3] >> (8 * (hh & 7))) & dmask);
+                if (q >= dc_nq) { status |= DGEN_ST_DEMAND; q = 0; }    // a malformed table (as the scan flags it)
+                if (q != dq) {
+                    dcl[dq * BM_BLOCK] = dacc;
+                    dq = q;
+                    dacc = dcl[q * BM_BLOCK];
+                }
+                const bool im = dd > 0.0;
+                const double ex = -dd;
+                const double tsw = ts_on ? (double)(float)(tq[hh & 3] * ts_mult) : 1.0;
+                b_net += dd;
+                b_ld += ld;
+                b_gen += g;
+                b_imp += im ? dd : 0.0;
+                b_exv += im ? 0.0 : ex * tsw;
+                exk += im ? 0.0 : ex;
+                peak = fmax(peak, dd);
+                dacc = fmax(dacc, dd);
+                if ((hh & 3) == 3) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) tq[j] = tn[j];
+                }
+            }
+            cur = nxt;
+        }
+        // ---- the month's bill (the oracle's year_bill step, month m) ----
+        lds[(0 * PH + bcur) * BM_BLOCK] = b_net;
+        lds[(1 * PH + bcur) * BM_BLOCK] = b_ld;
+        lds[(2 * PH + bcur) * BM_BLOCK] = b_gen;
+        lds[(3 * PH + bcur) * BM_BLOCK] = b_imp;
+        lds[(4 * PH + bcur) * BM_BLOCK] = b_exv;
+        dcl[dq * BM_BLOCK] = dacc;
+        BmMonth a;
+        double U = 0.0, crd = 0.0, impk = 0.0, bank_kwh = 0.0;
+        for (int p = 0; p < P; p++) {           // u[p] takes the net bin's place
+            const double net = lds[(0 * PH + p) * BM_BLOCK];
+            const double im = lds[(3 * PH + p) * BM_BLOCK];
+            impk += im;
+            double u;
+            if (mo == 0) {
+                double c = lds[(5 * PH + p) * BM_BLOCK];
+                if (net >= 0.0) {
+                    const double use = net < c ? net : c;
+                    u = net - use;
+                    c -= use;
+                } else {
+                    u = 0.0;
+                    c += -net;
+                }
+                lds[(5 * PH + p) * BM_BLOCK] = c;
+                bank_kwh += c;
+            } else if (mo == 1) {
+                u = net > 0.0 ? net : 0.0;
+                crd += (net < 0.0 ? -net : 0.0) * t.sell[p][0];
+            } else if (mo == 4) {
+                u = lds[(1 * PH + p) * BM_BLOCK];
+                crd += lds[(2 * PH + p) * BM_BLOCK] * t.sell[p][0];
+            } else {
+                u = im;
+                const double xv = lds[(4 * PH + p) * BM_BLOCK];
+                crd += ts_on ? xv : xv * t.sell[p][0];
+            }
+            lds[(0 * PH + p) * BM_BLOCK] = u;
+            U += u;
+        }
+        double ec = 0.0;                        // month_energy_charge
+        if (U > 0.0) {
+            if (NT == 1) {
+                for (int p = 0; p < P; p++) ec += lds[(0 * PH + p) * BM_BLOCK] * t.buy[p][0];
+            } else {
+                const double days = (double)c_days_in_month[m];
+                const double scale = (t.unit == 2) ? days : (t.unit == 1) ? peak : (t.unit == 3) ? peak * days : 1.0;
+                double prev = 0.0;
+                for (int k = 0; k < NT; k++) {
+                    const double hi = (k == NT - 1) ? INFINITY : t.cap[k] * scale;
+                    const double top = U < hi ? U : hi;
+                    double amt = top - prev;
+                    if (amt < 0.0) amt = 0.0;
+                    if (hi > prev) prev = hi;
+                    for (int p = 0; p < P; p++) ec += (lds[(0 * PH + p) * BM_BLOCK] / U) * amt * t.buy[p][k];
+                }
+            }
+        }
+        double bill = t.fixed;
+        a.cr = crd;
+        a.carry = 0.0;
+        if (mo == 0) {
+            bill += ec;
+            a.cr = 0.0;
+            if (m == 11) {
+                a.cr = bank_kwh * cfg.nm_yearend_sell_rate;
+                bill -= a.cr;
+            }
+            a.carry = bank_kwh;
+        } else if (mo == 1 || mo == 3) {
+            const double e = ec - crd - carry;
+            carry = e < 0.0 ? -e : 0.0;
+            bill += e < 0.0 ? 0.0 : e;
+            a.carry = carry;
+        } else if (mo == 4) {
+            bill += ec - crd;
+        } else {
+            bill += ec;
+            bill -= crd;
+        }
+        a.dflat = 0.0;
+        a.dtou = 0.0;
+        if (dem) {
+            a.dflat = dc_tier_charge(peak, dem->flat_cap[m], dem->flat_price[m], dem->flat_nt[m]);
+            for (int q = 0; q < dc_nq; q++)
+                a.dtou += dc_tier_charge(dcl[q * BM_BLOCK], dem->tou_cap[q], dem->tou_price[q], dem->tou_nt[q]);
+        }
+        a.ec = ec;
+        a.fixed = t.fixed;
+        a.total = (bill + a.dflat) + a.dtou;
+        a.imp = impk;
+        a.exk = exk;
+        a.billed = U;
+        a.peak = peak;
+        bm_month_store(S, (int64_t)m * n + i, a);
+    }
+    if (status) bm_flag(S, n, i, status);       // a demand schedule beyond the table's periods
+    else S.status[i] = 0;
+}
 #endif  // !DGEN_TU_SEARCH
 
 }  // namespace
@@ -8420,6 +8742,53 @@ int32_t dgen_batt_summary(dgen_ctx* c, const dgen_tables* T, const dgen_agents* 
     HIP_TRY(hipSetDevice(c->device));
     hipLaunchKernelGGL(k_batt_summary, dim3((unsigned)blocks), dim3(BS_BLOCK), 0, (hipStream_t)stream, *T, *A, *O,
                        c->cfg, n, c->battery, midmask, *out);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_bill_months(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const double* kw,
+                         const int32_t* tariff, int64_t n, const dgen_bill_opt* opt, const dgen_bill_out* out,
+                         void* stream) {
+    if (!c || !T || !A || !kw || !tariff || !out || n < 0) {
+        set_err("dgen_bill_months: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand)) {
+        set_err("dgen_bill_months: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    if (!A->load_row || !A->cf_row || !A->load_kwh || !A->flags) {
+        set_err("dgen_bill_months: missing agent column (load_row, cf_row, load_kwh, flags)");
+        return DGEN_E_ARG;
+    }
+    if (!out->status) {
+        set_err("dgen_bill_months: missing output member (status)");
+        return DGEN_E_ARG;
+    }
+    const bool battery = opt && opt->battery != 0;
+    if (battery && (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1)) {
+        set_err("dgen_bill_months: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not billed with battery = 1: the daily plan under constant "
+                "efficiencies only");
+        return DGEN_E_ARG;
+    }
+    const int64_t blocks = (n + BM_BLOCK - 1) / BM_BLOCK;
+    if (blocks > 0x7fffffff) {
+        set_err("dgen_bill_months: n = %lld exceeds the launch grid", (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    const int dc_nq = (T->max_dc_periods > 0 && T->max_dc_periods <= DCP) ? T->max_dc_periods : DCP;
+    const size_t lds = (size_t)(BM_PLANES * lds_half(T->max_periods) + dc_nq) * BM_BLOCK * sizeof(double);
+    HIP_TRY(hipSetDevice(c->device));
+    // after dgen_set_battery(0) the bank is 0: the plain form is the battery form's bits
+    if (battery && c->battery)
+        hipLaunchKernelGGL((k_bill_months<true>), dim3((unsigned)blocks), dim3(BM_BLOCK), lds, (hipStream_t)stream,
+                           *T, *A, c->cfg, kw, tariff, n, dc_nq, *out);
+    else
+        hipLaunchKernelGGL((k_bill_months<false>), dim3((unsigned)blocks), dim3(BM_BLOCK), lds, (hipStream_t)stream,
+                           *T, *A, c->cfg, kw, tariff, n, dc_nq, *out);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

@@ -724,6 +724,43 @@ class Engine:
                                               self.stream_handle()), "dgen_batt_summary")
         return res
 
+    def bill_months(self, batch: AgentBatch, kw, tariff=None, battery: bool = False,
+                    want=None) -> Dict[str, object]:
+        """Year-1 monthly bill breakdown of `batch` at kw[j] kW under tariff[j]
+        for device row j (dgen_bill_months, async on the current stream): the
+        profile rows replayed and billed month by month, no outputs and no
+        plane needed.  kw, tariff: device tensors or host arrays of batch.n
+        values in the batch's device order (batch.perm maps caller rows to
+        it); kw 0 is the no-system bill; tariff indexes the engine's tariff
+        table and need not be the agent's own (None: the batch's tariff0).
+        battery: g is the system output of the scan's peak-shaving dispatch at
+        kw instead of the PV output.  want: the members to compute (default all
+        of _lib.BILL_FIELDS).  Returns {member: [12, n] float64 device tensor,
+        month-major} plus "status" ([n] int32; an agent with a non-zero status
+        holds NaN).  The definitions are in include/dgen_hip.h."""
+        torch = _torch()
+        want = tuple(_lib.BILL_FIELDS if want is None else want)
+        bad = [k for k in want if k not in _lib.BILL_FIELDS]
+        if bad:
+            raise ValueError(f"bill_months: want must name members of {_lib.BILL_FIELDS} (got {want})")
+        n = batch.n
+        k = self._to_dev(kw, torch.float64).contiguous()
+        t = batch.cols["tariff0"] if tariff is None else self._to_dev(tariff, torch.int32).contiguous()
+        if k.dim() != 1 or k.numel() != n or t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"bill_months: kw and tariff must hold one value per agent ({n}), "
+                             f"got {tuple(k.shape)} and {tuple(t.shape)}")
+        res = {m: torch.empty((12, n), dtype=torch.float64, device=self.dev) for m in want}
+        res["status"] = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        if n == 0:
+            return res
+        bo = _lib.BillOut(**{m: _ptr(v) for m, v in res.items()})
+        opt = _lib.BillOpt(1 if battery else 0, 0)
+        _lib.check(self.lib.dgen_bill_months(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                             _ptr(k), _ptr(t), n, ctypes.byref(opt), ctypes.byref(bo),
+                                             self.stream_handle()), "dgen_bill_months")
+        self._keep["_bill_kw"] = (k, t)       # alive until the next call (stream order)
+        return res
+
     def brent_selftest(self, lo, hi, xatol, c2, x0, c1, maxn=64):
         torch = _torch()
         f = lambda v: self._to_dev(np.asarray(v, dtype=np.float64), torch.float64)

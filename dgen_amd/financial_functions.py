@@ -190,7 +190,7 @@ def _device_tables(eng, src: ProfileStore, b: PopulationBuilder):
     eng.set_switches(b.switches.array())
 
 
-def agent_device_bytes(eng, grid_metrics: bool = False) -> int:
+def agent_device_bytes(eng, grid_metrics: bool = False, bill_metrics: bool = False) -> int:
     """HBM one agent of a drop-in call holds while it is sized: the three fp64
     hourly planes (3 x 8760 x 8 B; every hourly mode computes them, and
     grid_metrics digests them in place whatever the mode), its share of the
@@ -198,15 +198,20 @@ def agent_device_bytes(eng, grid_metrics: bool = False) -> int:
     scratch slot per agent), the yearly and scalar outputs twice (the
     caller-order gather before the download) and the agent columns.
     grid_metrics: plus one plane's monthly digest (12 x (4 x 8 + 2 x 4) B) and
-    the 18 annual columns twice (the gather)."""
+    the 18 annual columns twice (the gather).  bill_metrics: plus one case's
+    monthly bill (the members bill_metrics reduces, 12 x 8 B each, status, and
+    the call's kW and tariff, 4 + 8 + 4 B) and the 18 annual columns twice."""
     k = 4096
     ws = int(eng.lib.dgen_workspace_bytes(k, k)) // k
     yearly = len(_lib.OUTPUT_YEARLY) * (_lib.MAXY + 1) * 8
     gm = (12 * (4 * 8 + 2 * 4) + 2 * 18 * 8) if grid_metrics else 0
+    if bill_metrics:
+        from .bill_metrics import MEMBERS
+        gm += 12 * 8 * len(MEMBERS) + 16 + 2 * 18 * 8
     return 3 * NH * 8 + ws + 2 * (yearly + 8 * len(_lib.OUTPUT_SCALARS)) + 8 * len(_lib.AGENT_COLUMNS) + gm
 
 
-def device_rows_budget(eng, frac: float = 0.3, grid_metrics: bool = False) -> int:
+def device_rows_budget(eng, frac: float = 0.3, grid_metrics: bool = False, bill_metrics: bool = False) -> int:
     """Largest agent count one sizing call puts on the device at a time:
     ``DGEN_MAX_ROWS`` if set, else frac x (free HBM + this process's cached,
     unused blocks) / agent_device_bytes.  frac 0.3: two sub-batches are
@@ -223,13 +228,15 @@ def device_rows_budget(eng, frac: float = 0.3, grid_metrics: bool = False) -> in
     share = max(1, int(os.environ.get("DGEN_WORKERS_PER_DEVICE", "1").strip() or 1))
     free, _total = torch.cuda.mem_get_info(eng.dev)
     spare = torch.cuda.memory_reserved(eng.dev) - torch.cuda.memory_allocated(eng.dev)
-    return max(1024, int(frac / share * (free + max(spare, 0)) / agent_device_bytes(eng, grid_metrics)))
+    return max(1024, int(frac / share * (free + max(spare, 0)) /
+                         agent_device_bytes(eng, grid_metrics, bill_metrics)))
 
 
 def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                 hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
-                keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False):
+                keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
+                bill_metrics: bool = False):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -246,15 +253,17 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     per-agent values: the bits of one call); keep_planes False: the planes
     are released after that and never downloaded (o[plane] is None).
     batt_metrics: each sub-batch also summarises its battery dispatch on the
-    device (batt_metrics.COLUMNS, per-agent values: the bits of one call)."""
+    device (batt_metrics.COLUMNS, per-agent values: the bits of one call).
+    bill_metrics: each sub-batch also bills its three cases month by month on
+    the device (bill_metrics.COLUMNS, per-agent values: the bits of one call)."""
     n = len(cols["load_kwh"])
     if max_rows is None:
-        max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics)
+        max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics, bill_metrics=bill_metrics)
     max_rows = max(1, int(max_rows))
     import torch
     try:
         return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
-                                grid_metrics, keep_planes, fixed_kw, batt_metrics)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -264,16 +273,16 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
         torch.cuda.empty_cache()
         return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
                            grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw,
-                           batt_metrics=batt_metrics)
+                           batt_metrics=batt_metrics, bill_metrics=bill_metrics)
 
 
 def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
                      grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None,
-                     batt_metrics: bool = False):
+                     batt_metrics: bool = False, bill_metrics: bool = False):
     n = len(cols["load_kwh"])
     if n <= max_rows:
         return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
-                                grid_metrics, keep_planes, fixed_kw, batt_metrics)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -290,7 +299,7 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         parts.append(_run_device_once(b, sub, src, tm, nw, hourly_async=True, hourly_device=False,
                                       grid_metrics=grid_metrics, keep_planes=keep_planes,
                                       fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi],
-                                      batt_metrics=batt_metrics))
+                                      batt_metrics=batt_metrics, bill_metrics=bill_metrics))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -305,6 +314,10 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
     if batt_metrics:
         from .batt_metrics import COLUMNS as BATT_COLUMNS
         for name in BATT_COLUMNS:
+            o[name] = np.concatenate([p[name] for p in parts])
+    if bill_metrics:
+        from .bill_metrics import COLUMNS as BILL_COLUMNS
+        for name in BILL_COLUMNS:
             o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
         if not keep_planes:
@@ -328,7 +341,8 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
 def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[dict] = None,
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                      hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True,
-                     fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False):
+                     fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
+                     bill_metrics: bool = False):
     """Size the batch in one device call (fixed_kw: evaluate caller row i at
     fixed_kw[i] kW instead, Engine.evaluate); net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
@@ -340,7 +354,9 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     digest of the three planes taken on the device (caller order); keep_planes
     False then releases the planes without a download (o[plane] is None).
     batt_metrics: o also holds batt_metrics.COLUMNS, the annual battery
-    dispatch summary of the sized batch (Engine.batt_summary, caller order)."""
+    dispatch summary of the sized batch (Engine.batt_summary, caller order).
+    bill_metrics: o also holds bill_metrics.COLUMNS, the annual bill breakdown
+    of the three cases under tariff_final (Engine.bill_months, caller order)."""
     import time
     import torch
     from .attachment import state_hourly
@@ -370,6 +386,10 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     if batt_metrics:
         from .batt_metrics import annual_columns as batt_columns
         bm = batt_columns(eng, batch, out)
+    blm = None
+    if bill_metrics:
+        from .bill_metrics import annual_columns as bill_columns
+        blm = bill_columns(eng, batch, out)
     gm = None
     if grid_metrics:
         from .grid_metrics import annual_columns
@@ -397,6 +417,8 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         o.update(gm)
     if bm is not None:
         o.update(bm)
+    if blm is not None:
+        o.update(blm)
     if timing is not None:
         timing.update(upload_s=t1 - t0, device_s=t2 - t1, download_s=time.perf_counter() - t2)
     return o
@@ -530,7 +552,8 @@ def _fixed_kw_values(df: pd.DataFrame, fixed_kw) -> np.ndarray:
 
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
-               grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False):
+               grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
+               bill_metrics: bool = False):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -575,7 +598,18 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     empty or power-limited, and capture_mid_frac, equiv_full_cycles,
     self_sufficiency_frac -- from a replay of the dispatch on the device
     (dgen_batt_summary) after each sub-batch's sizing or evaluation; it reads
-    no plane, so the columns are the same bits in every hourly mode."""
+    no plane, so the columns are the same bits in every hourly mode.
+    bill_metrics: the frame gains the 18 scalar columns bill_metrics.COLUMNS --
+    per case (baseline at 0 kW, pvonly at the last evaluated size, with_batt at
+    system_kw with the battery dispatched) the year-1 bill_energy_ /
+    bill_credit_ / bill_fixed_ / bill_demand_ / bill_total_ dollars and
+    bill_max_month_ (the month, 0 to 11, of the largest monthly total) -- from
+    a replay of the profile rows on the device (dgen_bill_months) after each
+    sub-batch's sizing or evaluation; no plane is read, so the columns are the
+    same bits in every hourly mode and sub-batching.  All three cases are
+    billed under tariff_final, the sticky tariff after both runs: the pvonly
+    columns therefore reproduce first_year_elec_bill_with_system only where
+    the storage rate switch did not move the tariff."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
@@ -590,7 +624,7 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     o = _run_device(b, cols, src, dev_t, net_weights, hourly_async=hourly in ("lazy", "array", "list"),
                     hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
                     keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed,
-                    batt_metrics=batt_metrics)
+                    batt_metrics=batt_metrics, bill_metrics=bill_metrics)
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -663,6 +697,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
         from .batt_metrics import COLUMNS as BATT_COLUMNS
         for name in BATT_COLUMNS:
             out[name] = o[name]
+    if bill_metrics:
+        from .bill_metrics import COLUMNS as BILL_COLUMNS
+        for name in BILL_COLUMNS:
+            out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:
         # download_wait_s: time the frame assembly waited for the hourly planes
@@ -673,13 +711,15 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
                hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
-               grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False):
+               grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
+               bill_metrics: bool = False):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
     agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
     grid_metrics: size_frame's 18 per-agent grid-exchange columns.  fixed_kw:
     size_frame's (a column name or an aligned array: the chunk's agents are
     evaluated at those sizes instead of being sized).  batt_metrics:
-    size_frame's per-agent battery dispatch columns (batt_diag_*)."""
+    size_frame's per-agent battery dispatch columns (batt_diag_*).
+    bill_metrics: size_frame's 18 per-agent year-1 bill columns (bill_*)."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -693,7 +733,7 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     # kernel's fixed-order tree agree to rounding (parity test: 1e-12 relative)
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
                            net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics,
-                           fixed_kw=fixed_kw, batt_metrics=batt_metrics)
+                           fixed_kw=fixed_kw, batt_metrics=batt_metrics, bill_metrics=bill_metrics)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

@@ -853,6 +853,106 @@ int32_t dgen_batt_summary(dgen_ctx* ctx, const dgen_tables* tables, const dgen_a
                           const dgen_outputs* out, int64_t n, const dgen_batt_summary_opt* opt,
                           const dgen_batt_summary_out* summary, void* stream);
 
+/* Year-1 monthly bill breakdown per agent (additive to ABI 14): "bill agent i
+ * at kw[i] kW under tariff[i]", month by month -- the year-1 bill of the
+ * oracle (oracle/orc.c: bin_year, month_energy_charge, year_bill, year_demand,
+ * dc_tier_charge) at degradation factor 1 and escalation factor 1, with every
+ * ingredient the year-lane kernels reduce to one scalar.  kw: [n] device
+ * doubles, 0 is valid (the no-system bill); tariff: [n] device int32 indices
+ * into tables->tariffs, the caller's choice (not necessarily the agent's own:
+ * the what-if bill under any tariff of the table).  A replay from the profile
+ * rows, as dgen_batt_summary is: no dgen_outputs, no plane, no workspace.
+ * One lane per agent, the year in hour order.  Per agent i:
+ *   ls  = load_kwh / shape_sum[load_row]
+ *   cs6 = (((kw x 1000) x 0.96) / 1000) / 1e6
+ * and for every hour h of the non-leap year, in order:
+ *   ld = (double)shape[h] x ls;  pv = (double)cf[h] x cs6
+ *   g  = pv                                       (opt NULL or battery = 0)
+ *   g  = pv + f  with battery = 1: the system output of the scan's
+ *        peak-shaving dispatch at this kw (bank and power from kw / 0.8 / 2,
+ *        kw / 0.8 as dgen_batt_summary sizes them; the day's plan, the month
+ *        floor and the hour's step are the scan's own device functions on
+ *        ld - pv, f = -cc charging, dd discharging: the value k_hourly_batt
+ *        stores in its system-output scratch plane, bit for bit); the bank
+ *        is 0 (g = pv) after dgen_set_battery(0) or when it is not positive
+ *   d  = ld - g
+ * Calendar: the year starts on a Monday, hours with (h % 168) >= 120 are
+ * weekend; the hour's period p is the tariff's wkday / wkend[month][h % 24]
+ * (clamped to P - 1).  Per (month, period), fp64 sequential sums in hour
+ * order, all from 0:
+ *   net += d;  lbin += ld;  gbin += g
+ *   imp += d            when d > 0
+ *   exv += (-d) x ts[h] otherwise, ts[h] = 1 without the TS sell rate
+ * The TS sell rate applies when tariff.mo == 2, the agent is not CA (flags
+ * bit 1), wholesale_row >= 0 (the column and price_mult given) and
+ * tables->wholesale != NULL; then
+ *   ts[h] = (double)(float)(wholesale[h] x price_mult).
+ * Per month: peak = max over its hours of d, 0 without import; export_kwh =
+ * the sequential sum of max(-d, 0) (kWh, also under TS).  Demand charges are
+ * on when cfg.skip_demand_charges == 0 and tariff.dc names a record (1 ..
+ * n_demand); then the peak of demand period q is the max of d (0 without
+ * import) over the hours the record's wkday / wkend put in q.
+ * Then the 12 months in order, with credit[p] (kWh, mo 0) and carry ($, mo 1
+ * and 3) starting at 0 and living across the months, exactly as year_bill:
+ *   mo 0  per p ascending: net >= 0: use = min(net, credit[p]), u[p] = net -
+ *         use, credit[p] -= use; else u[p] = 0, credit[p] += -net.
+ *         bill = fixed + E(u); December: bill -= (sum_p credit[p]) x
+ *         nm_yearend_sell_rate
+ *   mo 1  u[p] = max(net, 0); cr = sum_p max(-net, 0) x sell[p][0];
+ *         e = E(u) - cr - carry; carry = max(-e, 0); bill = fixed + max(e, 0)
+ *   mo 4  u[p] = lbin; cr = sum_p gbin x sell[p][0]; bill = fixed + (E(u) - cr)
+ *   mo 2, 3 (and any other value)  u[p] = imp; cr = sum_p exv (TS) or
+ *         sum_p exv x sell[p][0]; mo 3: e, carry and bill as mo 1;
+ *         else bill = (fixed + E(u)) - cr
+ * E(u) = month_energy_charge: U = sum_p u[p]; 0 unless U > 0; one tier:
+ * sum_p u[p] x buy[p][0]; else over tiers k ascending, hi = cap[k] x scale
+ * (infinite for the last tier; scale 1, days (unit 2), peak (unit 1) or peak x
+ * days (unit 3)), amt = max(min(U, hi) - prev, 0), prev = max(prev, hi), and
+ * per p ascending the charge grows by ((u[p] / U) x amt) x buy[p][k].
+ * Members, each [12][n] month-major (value (m, i) at [m x n + i]):
+ *   energy_charge  E(u)
+ *   export_credit  cr of mo 1 to 4; mo 0: 0, except December's
+ *                  (sum_p credit[p]) x nm_yearend_sell_rate
+ *   fixed_charge   tariff.fixed
+ *   demand_flat    dc_tier_charge of `peak` over the record's month tiers
+ *   demand_tou     sum over q ascending of dc_tier_charge of period q's peak;
+ *                  both 0 when demand charges are off
+ *   total          (bill + demand_flat) + demand_tou.  For mo 1 and 3 the bill
+ *                  carries the floor at 0: energy_charge - export_credit -
+ *                  (the carry before the month) may be negative, and
+ *                  total = fixed + max(that, 0) + demand
+ *   carry          after the month: sum_p credit[p] in kWh (mo 0; December's
+ *                  is the bank the true-up pays out), the carried dollars
+ *                  (mo 1, 3), 0 otherwise
+ *   import_kwh     sum_p imp
+ *   export_kwh     as above
+ *   billed_kwh     U
+ *   peak_kw        peak
+ * Every sum over periods and over tiers runs in ascending order, and a x b + c
+ * stays two roundings (the library is built with -ffp-contract=off).
+ * status[i] ([n], required): 0, or DGEN_ST_TARIFF for an index outside
+ * 0 .. n_tariffs - 1 (or a tariff whose P exceeds tables->max_periods), the
+ * tariff's own flags (DGEN_ST_EMPTY_EC, _UNIT, _DEMAND; _DEMAND also for a
+ * demand schedule beyond tables->max_dc_periods), DGEN_ST_BOUNDS for a kw that
+ * is not finite or is negative; DGEN_ST_YEARS does not apply.  An agent with a
+ * non-zero status gets NaN in every double member.  A NULL member is not
+ * written.  No atomics and no cross-lane sums: run-to-run identical.  Table
+ * and agent-column checks are dgen_batt_summary's.  battery = 1 under
+ * batt_update_hours == 1 or batt_loss_model == 1 returns DGEN_E_ARG.
+ * Utilityrate5's counterparts are its year1_monthly_* and charge_w_sys_*_ym
+ * outputs, which the reference drops.                                       */
+typedef struct { int32_t battery; int32_t pad; } dgen_bill_opt;      /* NULL: battery = 0 */
+
+typedef struct {   /* each [12][n] month-major, any may be NULL, except status [n] */
+    double *energy_charge, *export_credit, *fixed_charge, *demand_flat, *demand_tou, *total,
+           *carry, *import_kwh, *export_kwh, *billed_kwh, *peak_kw;
+    int32_t *status;
+} dgen_bill_out;
+
+int32_t dgen_bill_months(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                         const double* kw, const int32_t* tariff, int64_t n, const dgen_bill_opt* opt,
+                         const dgen_bill_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
