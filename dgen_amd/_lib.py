@@ -28,6 +28,7 @@ ST_YEARS = 0x10
 ST_SCRATCH = 0x20
 ST_ZERO_LOAD = 0x40
 ST_DEMAND = 0x80
+ST_HOURLY_FORM = 0x100   # dgen_batt_curve only: the point's tariff needs the per-year hourly pass
 ST_FATAL = ST_BOUNDS | ST_TARIFF | ST_YEARS | ST_SCRATCH | ST_UNIT | ST_DEMAND
 
 _vp = ctypes.c_void_p
@@ -154,6 +155,18 @@ class BillOut(ctypes.Structure):
     _fields_ = [(name, _vp) for name in BILL_FIELDS] + [("status", _vp)]
 
 
+BATT_CURVE_F64 = ["npv", "payback_raw", "total_cost", "bank_kwh", "power_kw", "bill_w_year1", "bill_wo_year1",
+                  "lifetime_savings"]
+BATT_CURVE_I32 = ["tariff", "switched", "status"]
+BATT_CURVE_FIELDS = BATT_CURVE_F64 + BATT_CURVE_I32
+BATT_CURVE_MAX_POINTS = 16   # include/dgen_hip.h DGEN_BATT_CURVE_MAX_POINTS
+
+
+class BattCurveOut(ctypes.Structure):
+    """dgen_batt_curve_out: [K][n] point-major device planes, any may be NULL."""
+    _fields_ = [(name, _vp) for name in BATT_CURVE_FIELDS]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -172,7 +185,7 @@ EXPORTED = [
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
-    "dgen_bill_months",
+    "dgen_bill_months", "dgen_batt_curve",
 ]
 
 
@@ -264,6 +277,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_bill_months.restype = _i32
     L.dgen_bill_months.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _vp, _vp, _i64,
                                    ctypes.POINTER(BillOpt), ctypes.POINTER(BillOut), _vp]
+    L.dgen_batt_curve.restype = _i32
+    L.dgen_batt_curve.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
+                                  _i64, _i32, _vp, _vp, ctypes.POINTER(BattCurveOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

@@ -1,0 +1,192 @@
+"""Battery size what-if: with-battery economics at caller-given banks.
+
+The reference sizes the battery from two constants (pv_to_batt_ratio = 0.8,
+batt_capacity_to_power_ratio = 2.0): the bank is kW* / 0.8 kWh with kW* / 0.8 /
+2 kW.  ``Engine.batt_curve`` (dgen_batt_curve) runs the PV+battery forward pass
+of a sized batch at any other bank -- dispatch replay, N-year bill, Cashloan --
+K points per agent in one launch (the definitions are in include/dgen_hip.h).
+This module carries that up:
+
+    ratio_points(system_kw, pv_to_batt, hours)   [K, n] kWh and kW point arrays from ratios
+    curve_outputs(engine, batch, out, kwh, kw)   the curve of a sized output dict, caller order
+    best_point(curve)                            per agent the valid point of largest NPV
+    annual_columns(engine, batch, out, spec)     the per-agent columns of the drop-in switch
+                                                 (financial_functions.size_frame(batt_sizing=spec))
+
+The kernel covers the tariffs that bill from monthly bins (metering options 0,
+1, 4; tier units 0, 2; no billed demand charge); a point under another form
+carries _lib.ST_HOURLY_FORM and NaN, and is never a best point.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+
+REF_PV_TO_BATT = 0.8     # the reference's pv_to_batt_ratio
+REF_HOURS = 2.0          # the reference's batt_capacity_to_power_ratio
+PREFIX = "batt_opt_"
+COLUMNS = tuple(PREFIX + k for k in ("kwh", "kw", "npv", "payback", "point", "npv_gain", "status"))
+# status bits that leave a point without a value
+INVALID = (_lib.ST_BOUNDS | _lib.ST_TARIFF | _lib.ST_YEARS | _lib.ST_SCRATCH | _lib.ST_UNIT | _lib.ST_DEMAND
+           | _lib.ST_HOURLY_FORM)
+
+
+def _xp(t):
+    if isinstance(t, np.ndarray):
+        return np
+    import torch
+    return torch
+
+
+def ratio_points(system_kw, pv_to_batt: Sequence[float] = (REF_PV_TO_BATT,),
+                 hours: Sequence[float] = (REF_HOURS,)) -> Tuple[object, object]:
+    """The (kwh, kw) point arrays, each [K, n] with K = len(pv_to_batt) x
+    len(hours), ratio-major: point k = a x len(hours) + b has
+    kwh = system_kw / pv_to_batt[a] and kw = kwh / hours[b] -- the reference's
+    own expressions, so (0.8, 2.0) is its bank bit for bit.  system_kw: [n], a
+    numpy array or a tensor (the result is of the same kind).  Every ratio and
+    duration must be finite and positive."""
+    r = [float(v) for v in pv_to_batt]
+    h = [float(v) for v in hours]
+    if not r or not h or not all(np.isfinite(v) and v > 0.0 for v in r + h):
+        raise ValueError(f"ratio_points: ratios and hours must be finite and positive (got {r}, {h})")
+    if len(r) * len(h) > _lib.BATT_CURVE_MAX_POINTS:
+        raise ValueError(f"ratio_points: {len(r)} x {len(h)} points exceed {_lib.BATT_CURVE_MAX_POINTS}")
+    xp = _xp(system_kw)
+    kwh, kw = [], []
+    for a in r:
+        e = system_kw / a
+        for b in h:
+            kwh.append(e)
+            kw.append(e / b)
+    return xp.stack(kwh), xp.stack(kw)
+
+
+def _inverse(engine, perm):
+    if perm is None:
+        return None
+    import torch
+    p = np.asarray(perm, np.int64)
+    iv = np.empty_like(p)
+    iv[p] = np.arange(p.size, dtype=np.int64)
+    return engine._to_dev(iv, torch.int64)
+
+
+def curve_outputs(engine, batch, out, kwh, kw=None, want: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """Engine.batt_curve of a batch sized (or evaluated) into `out`, with kwh /
+    kw given and the members returned in caller order (batch.perm):
+    {member: [K, n] device tensor}."""
+    import torch
+    e = engine._to_dev(kwh, torch.float64)
+    p = None if kw is None else engine._to_dev(kw, torch.float64)
+    if batch.perm is not None:
+        pm = engine._to_dev(np.asarray(batch.perm, np.int64), torch.int64)
+        e = e.index_select(e.dim() - 1, pm)
+        p = None if p is None else p.index_select(p.dim() - 1, pm)
+    d = engine.batt_curve(batch, out, e, p, want)
+    inv = _inverse(engine, batch.perm)
+    if inv is None:
+        return d
+    return {k: v.index_select(1, inv) for k, v in d.items()}
+
+
+def best_point(curve: Dict[str, object]):
+    """Per agent the index of the valid point of largest NPV ([n] int64; numpy
+    or torch as the curve is): a point is valid when its status has no INVALID
+    bit and its npv is not NaN; the first point wins a tie; -1 where no point
+    is valid."""
+    npv, st = curve["npv"], curve["status"]
+    xp = _xp(npv)
+    ok = ((st & INVALID) == 0) & ~xp.isnan(npv)
+    K = npv.shape[0]
+    best = xp.full_like(npv[0], -np.inf)
+    if xp is np:
+        idx = np.full(npv.shape[1], -1, np.int64)
+    else:
+        idx = xp.full((npv.shape[1],), -1, dtype=xp.int64, device=npv.device)
+    for k in range(K):
+        take = ok[k] & ((idx < 0) | (npv[k] > best))
+        best = xp.where(take, npv[k], best)
+        idx = xp.where(take, xp.full_like(idx, k), idx)
+    return idx
+
+
+def _pick(xp, v, idx, fill):
+    """v[idx[i], i], fill where idx is -1."""
+    safe = xp.where(idx < 0, xp.zeros_like(idx), idx)
+    if xp is np:
+        g = v[safe, np.arange(v.shape[1])]
+    else:
+        g = v.gather(0, safe.view(1, -1))[0]
+    return xp.where(idx < 0, xp.full_like(g, fill), g)
+
+
+def summarize(curve: Dict[str, object], ref_point: int) -> Dict[str, object]:
+    """The COLUMNS of a curve ([n] each; numpy or torch as the curve is), with
+    ref_point the index of the reference's point in it:
+      batt_opt_point     best_point(curve)
+      batt_opt_kwh, _kw  the installed bank and power at it (NaN where -1)
+      batt_opt_npv, batt_opt_payback   npv and payback_raw at it
+      batt_opt_npv_gain  batt_opt_npv minus the npv at ref_point (NaN where
+                         either is missing)
+      batt_opt_status    the best point's status; where no point is valid the
+                         bitwise or of every point's status"""
+    xp = _xp(curve["npv"])
+    idx = best_point(curve)
+    res = {PREFIX + "kwh": _pick(xp, curve["bank_kwh"], idx, np.nan),
+           PREFIX + "kw": _pick(xp, curve["power_kw"], idx, np.nan),
+           PREFIX + "npv": _pick(xp, curve["npv"], idx, np.nan),
+           PREFIX + "payback": _pick(xp, curve["payback_raw"], idx, np.nan),
+           PREFIX + "point": idx}
+    res[PREFIX + "npv_gain"] = res[PREFIX + "npv"] - curve["npv"][ref_point]
+    st = curve["status"]
+    allst = st[0]
+    for k in range(1, st.shape[0]):
+        allst = allst | st[k]
+    res[PREFIX + "status"] = _pick(xp, st, idx, 0) | xp.where(idx < 0, allst, xp.zeros_like(allst))
+    return res
+
+
+def grid(spec) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
+    """size_frame's batt_sizing spec as (pv_to_batt, hours): a dict with either
+    key, a (pv_to_batt, hours) pair, or True for the default grid."""
+    if spec is True:
+        return (0.4, 0.8, 1.6), (1.0, 2.0, 4.0)
+    if isinstance(spec, dict):
+        bad = set(spec) - {"pv_to_batt", "hours"}
+        if bad:
+            raise ValueError(f"batt_sizing: unknown keys {sorted(bad)}")
+        return tuple(spec.get("pv_to_batt", (REF_PV_TO_BATT,))), tuple(spec.get("hours", (REF_HOURS,)))
+    r, h = spec
+    return tuple(r), tuple(h)
+
+
+def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
+    """The drop-in switch's per-agent columns (COLUMNS) of a sized output dict
+    as host arrays in caller order: the curve over ratio_points(system_kw,
+    *grid(spec)) with the reference's point (0.8, 2.0) appended as the last
+    point, reduced by summarize().  float64, except batt_opt_point and
+    batt_opt_status (int64).  Only these [n] vectors cross to the host."""
+    import torch
+    r, h = grid(spec)
+    skw = out["system_kw"]
+    kwh, kw = ratio_points(skw, r, h)
+    rk, rp = ratio_points(skw, (REF_PV_TO_BATT,), (REF_HOURS,))
+    kwh, kw = torch.cat([kwh, rk]), torch.cat([kw, rp])
+    if kwh.shape[0] > _lib.BATT_CURVE_MAX_POINTS:
+        raise ValueError(f"batt_sizing: {kwh.shape[0]} points (the reference's included) exceed "
+                         f"{_lib.BATT_CURVE_MAX_POINTS}")
+    # an unsized agent's system_kw may be NaN: its points are flagged, not read
+    d = engine.batt_curve(batch, out, kwh, kw, ("npv", "payback_raw", "bank_kwh", "power_kw", "status"))
+    s = summarize(d, int(kwh.shape[0]) - 1)
+    inv = _inverse(engine, batch.perm)
+    res = {}
+    for k in COLUMNS:
+        t = s[k] if inv is None else s[k].index_select(0, inv)
+        if t.dtype == torch.int32:
+            t = t.to(torch.int64)
+        res[k] = t.cpu().numpy()
+    return res

@@ -7221,6 +7221,341 @@ k_bill_months(dgen_tables T, dgen_agents A, dgen_cfg cfg, const double* __restri
     if (status) bm_flag(S, n, i, status);       // a demand schedule beyond the table's periods
     else S.status[i] = 0;
 }
+
+// ---------------------------------------------------------------------------
+// Battery size what-if (dgen_batt_curve; the definition is in
+// include/dgen_hip.h): the PV+battery run of a sized batch at caller-given
+// banks.  One lane per (agent, point), lane k n + i: a wave holds 64
+// neighbouring agents of one point and walks the year as a k_batt_summary wave
+// does (the same day-ahead 16-B row loads, the dispatch through the scan's own
+// device functions), with k_bill_months' per-day schedule row beside them.
+// LDS, [plane][period][lane] doubles (a wave's 64 lanes contiguous): the
+// twelve months' load bins, the twelve months' system-output bins, the NEM
+// kWh credit bank and the month's billed kWh; the current period's two bins
+// stay in registers until the period changes.  After hour 8759 the lane bills
+// the no-system year once and the N analysis years from the bins at
+// net = L - s_y G (the year-lane kernels' bins form), the tariff read from
+// global memory, and steps the Cashloan year by year: the payback chain is
+// the oracle's, the NPV is the forward sum of atcf_y rr^y (rr^y a running
+// product) instead of the Horner chain from year N, which would need the N
+// flows kept per lane.  No atomics, no cross-lane traffic.
+// ---------------------------------------------------------------------------
+constexpr int BC_BLOCK = 64;
+constexpr int BC_PLANES = 26;     // 12 load months, 12 system-output months, credit bank, billed kWh
+struct BcDay {
+    f32x4 s[6];
+    i32x4 c[6];
+    uint64_t e[3];                // the day's energy period row
+};
+__device__ __forceinline__ void bc_day_load(const float* __restrict__ shp, const int32_t* __restrict__ cfp,
+                                            const char* esch, int d, int m, BcDay& r) {
+#pragma unroll
+    for (int q = 0; q < 6; q++) {
+        r.s[q] = *reinterpret_cast<const f32x4*>(shp + d * 24 + 4 * q);
+        r.c[q] = *reinterpret_cast<const i32x4*>(cfp + d * 24 + 4 * q);
+    }
+    // wkend[12][24] follows wkday[12][24] in dgen_tariff
+    const uint64_t* a = reinterpret_cast<const uint64_t*>(esch + ((d % 7) >= 5 ? 288 : 0) + 24 * m);
+    r.e[0] = a[0]; r.e[1] = a[1]; r.e[2] = a[2];
+}
+struct BcPoint {
+    double npv, payback, cost, bank, power, w1, wo1, life;
+    int tariff, switched, status;
+};
+__device__ __forceinline__ void bc_store(const dgen_batt_curve_out& S, int64_t o, const BcPoint& a) {
+    if (S.npv) S.npv[o] = a.npv;
+    if (S.payback_raw) S.payback_raw[o] = a.payback;
+    if (S.total_cost) S.total_cost[o] = a.cost;
+    if (S.bank_kwh) S.bank_kwh[o] = a.bank;
+    if (S.power_kw) S.power_kw[o] = a.power;
+    if (S.bill_w_year1) S.bill_w_year1[o] = a.w1;
+    if (S.bill_wo_year1) S.bill_wo_year1[o] = a.wo1;
+    if (S.lifetime_savings) S.lifetime_savings[o] = a.life;
+    if (S.tariff) S.tariff[o] = a.tariff;
+    if (S.switched) S.switched[o] = a.switched;
+    if (S.status) S.status[o] = a.status;
+}
+__device__ __forceinline__ void bc_flag(const dgen_batt_curve_out& S, int64_t o, int tariff, int switched,
+                                        int status) {
+    const double q = __builtin_nan("");
+    const BcPoint z = {q, q, q, q, q, q, q, q, tariff, switched, status};
+    bc_store(S, o, z);
+}
+
+// oracle year_bill (options 0, 1, 4) from the lane's (month, period) bins at
+// net = L - s G; gen false: the no-system year (G = 0).  lds: the lane's column.
+__device__ double bc_year_bill(const dgen_tariff& t, double* lds, int PH, double s, bool gen, double yearend) {
+    const int P = t.P, NT = t.T, mo = t.mo;
+    double* const cred = lds + (size_t)24 * PH * BC_BLOCK;
+    double* const ub = cred + (size_t)PH * BC_BLOCK;
+    for (int p = 0; p < P; p++) cred[p * BC_BLOCK] = 0.0;
+    double total = 0.0, carry = 0.0;
+    for (int m = 0; m < 12; m++) {
+        double U = 0.0, cr = 0.0;
+        for (int p = 0; p < P; p++) {
+            const double L = lds[(m * PH + p) * BC_BLOCK];
+            const double G = gen ? s * lds[((12 + m) * PH + p) * BC_BLOCK] : 0.0;
+            const double net = L - G;
+            double u;
+            if (mo == 0) {
+                double c = cred[p * BC_BLOCK];
+                if (net >= 0.0) {
+                    const double use = net < c ? net : c;
+                    u = net - use;
+                    c -= use;
+                } else {
+                    u = 0.0;
+                    c += -net;
+                }
+                cred[p * BC_BLOCK] = c;
+            } else if (mo == 1) {
+                u = net > 0.0 ? net : 0.0;
+                cr += (net < 0.0 ? -net : 0.0) * t.sell[p][0];
+            } else {
+                u = L;
+                cr += G * t.sell[p][0];
+            }
+            ub[p * BC_BLOCK] = u;
+            U += u;
+        }
+        double ec = 0.0;                        // month_energy_charge, units 0 and 2
+        if (U > 0.0) {
+            if (NT == 1) {
+                for (int p = 0; p < P; p++) ec += ub[p * BC_BLOCK] * t.buy[p][0];
+            } else {
+                const double scale = (t.unit == 2) ? (double)c_days_in_month[m] : 1.0;
+                double prev = 0.0;
+                for (int k = 0; k < NT; k++) {
+                    const double hi = (k == NT - 1) ? INFINITY : t.cap[k] * scale;
+                    const double top = U < hi ? U : hi;
+                    double amt = top - prev;
+                    if (amt < 0.0) amt = 0.0;
+                    if (hi > prev) prev = hi;
+                    for (int p = 0; p < P; p++) ec += (ub[p * BC_BLOCK] / U) * amt * t.buy[p][k];
+                }
+            }
+        }
+        double bill = t.fixed;
+        if (mo == 0) {
+            bill += ec;
+            if (m == 11) {
+                double c = 0.0;
+                for (int p = 0; p < P; p++) c += cred[p * BC_BLOCK];
+                bill -= c * yearend;
+            }
+        } else if (mo == 1) {
+            const double e = ec - cr - carry;
+            carry = e < 0.0 ? -e : 0.0;
+            bill += e < 0.0 ? 0.0 : e;
+        } else {
+            bill += ec - cr;
+        }
+        total += bill;
+    }
+    return total;
+}
+
+__global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_batt_curve(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t n, int K, int batt_on,
+             const double* __restrict__ kwh_pts, const double* __restrict__ kw_pts, dgen_batt_curve_out S) {
+    const int64_t o = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x;      // k n + i
+    if (o >= (int64_t)K * n) return;
+    const int64_t i = o % n;
+    const int PH = lds_half(T.max_periods);
+    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BC_BLOCK]
+    const int st = O.status[i];
+    int tariff = O.tariff_final[i], switched = O.switched[i];
+    if (st & (DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_YEARS)) {       // the sizing call left the agent unsized
+        bc_flag(S, o, tariff, switched, st);
+        return;
+    }
+    const double desired_kwh = kwh_pts[o];
+    const double desired_kw = kw_pts ? kw_pts[o] : desired_kwh / 2.0;
+    int status = 0;
+    if (!(desired_kwh >= 0.0) || isinf(desired_kwh)) status |= DGEN_ST_BOUNDS;
+    else if (kw_pts && desired_kwh > 0.0 && (!(desired_kw > 0.0) || isinf(desired_kw))) status |= DGEN_ST_BOUNDS;
+    if (st & DGEN_ST_UNIT) status |= DGEN_ST_HOURLY_FORM;
+    const int N = A.econ_life[i];
+    if (N < 1 || N > MAXY) status |= DGEN_ST_YEARS;
+    if (tariff < 0 || tariff >= T.n_tariffs) status |= DGEN_ST_TARIFF;
+    if (status) {
+        bc_flag(S, o, tariff, switched, status);
+        return;
+    }
+    const bool is_res = (A.flags[i] & 1) != 0;
+    const double kw_star = O.system_kw[i];
+    double bank = 0.0, power = 0.0;
+    if (batt_on) batt_size(desired_kw, desired_kwh, is_res ? 240.0 : 500.0, cfg, &bank, &power);
+    double otc = 0.0;
+    if (bank > 0.0) {       // the storage rate switch, sticky on the state the sizing call left
+        int nt = -1;
+        otc = rate_switch(T.switches + A.sw_storage_off[i], A.sw_storage_cnt[i], bank, &nt);
+        if (nt != -1) {
+            tariff = nt;
+            switched = 1;
+        }
+    }
+    if (tariff < 0 || tariff >= T.n_tariffs) {
+        bc_flag(S, o, tariff, switched, DGEN_ST_TARIFF);
+        return;
+    }
+    const dgen_tariff& t = T.tariffs[tariff];
+    const int P = t.P;
+    // a table whose max_periods does not cover the tariff is malformed
+    if (P < 1 || P > PH || t.T < 1 || t.T > MAXT) status |= DGEN_ST_TARIFF;
+    // hourly imports, billed demand charges, kWh/kW tiers: the per-year hourly pass this kernel lacks
+    if (net_hourly(t) || peak_unit(t) || tariff_demand(T, cfg, t) != nullptr) status |= DGEN_ST_HOURLY_FORM;
+    if (status) {
+        bc_flag(S, o, tariff, switched, status);
+        return;
+    }
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double ls = A.load_kwh[i] / T.shape_sum[lr];
+    const double cs6 = (((kw_star * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    const char* const esch = reinterpret_cast<const char*>(t.wkday);
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    double soc = cfg.batt_init_soc;
+    BcDay cur, nxt;
+    bc_day_load(shp, cfp, esch, 0, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        for (int p = 0; p < P; p++) {
+            lds[(m * PH + p) * BC_BLOCK] = 0.0;
+            lds[((12 + m) * PH + p) * BC_BLOCK] = 0.0;
+        }
+        int bcur = 0;
+        double b_ld = 0.0, b_gen = 0.0, mfloor = 0.0;
+        const int d_end = c_month_start_day[m + 1];
+        for (int d = c_month_start_day[m]; d < d_end; d++) {
+            {   // the next day's rows (December 31 loads itself again)
+                const int dn = d < 364 ? d + 1 : 364;
+                bc_day_load(shp, cfp, esch, dn, dn < d_end ? m : m + 1, nxt);
+            }
+            double dv[24];
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++)
+                dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+            sort24_desc(dv);
+            const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+            double target = day_target_sorted(dv, power, avail0);
+            {   // dgen_cfg.batt_month_floor: the month's target never falls
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                const double ld = (double)opaque_f(cur.s[hh >> 2][hh & 3]) * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                const HourStep hs = batt_hour(ld - pv, pv, target, power, bank, soc, cfg, inv_eta_in, in_per_bank,
+                                              out_per_bank);
+                int p = (int)((cur.e[hh >> 3] >> (8 * (hh & 7))) & 0xffu);
+                p = p < P ? p : P - 1;                  // a schedule beyond P: never past the lane's bins
+                if (p != bcur) {
+                    lds[(m * PH + bcur) * BC_BLOCK] = b_ld;
+                    lds[((12 + m) * PH + bcur) * BC_BLOCK] = b_gen;
+                    bcur = p;
+                    b_ld = lds[(m * PH + p) * BC_BLOCK];
+                    b_gen = lds[((12 + m) * PH + p) * BC_BLOCK];
+                }
+                b_ld += ld;
+                b_gen += hs.sys;
+            }
+            cur = nxt;
+        }
+        lds[(m * PH + bcur) * BC_BLOCK] = b_ld;
+        lds[((12 + m) * PH + bcur) * BC_BLOCK] = b_gen;
+    }
+    // ---- the N years' bills (oracle orc_ur5) and the Cashloan (orc_cashloan), year by year ----
+    const double rate_base = 1.0 + (A.inflation[i] * 100.0) * 0.01 + (A.escalator[i] * 100.0) * 0.01;
+    const double sys_base = 1.0 - (A.pv_deg[i] * 100.0) * 0.01;
+    const double vor = A.vor[i];
+    const double system_costs = (kw_star > 0.0) ? A.capex_combined[i] * kw_star : A.capex[i] * kw_star;
+    const double batt_costs = A.batt_capex_kwh[i] * bank * 0.7;
+    const double C = ((system_costs + batt_costs) * A.ccm[i]) + 0.0 + otc;
+    const int market = is_res ? 0 : 1, depr_type = is_res ? 0 : 2;
+    const double infl = (A.inflation[i] * 100.0) * 0.01;
+    const double real = (A.real_discount[i] * 100.0) * 0.01;
+    const double nom = (1.0 + real) * (1.0 + infl) - 1.0;
+    const double fed = ((A.tax_rate[i] * 100.0) * 0.7) * 0.01, sta = ((A.tax_rate[i] * 100.0) * 0.3) * 0.01;
+    const double debt = (100.0 - (A.down_payment[i] * 100.0)) * 0.01 * C;
+    const double r = cfg.loan_rate_pct * 0.01;
+    const int term = A.loan_term[i];
+    double pmt = 0.0;
+    if (term > 0 && debt != 0.0) {
+        if (r != 0.0) {
+            const double f = pow_seq(1.0 + r, term);
+            pmt = debt * r / (1.0 - 1.0 / f);
+        } else {
+            pmt = debt / (double)term;
+        }
+    }
+    double itc = A.itc_frac[i] * 0.01 * C;
+    if (itc > cfg.itc_fed_max) itc = cfg.itc_fed_max;
+    const double basis = C - 0.5 * itc;
+    const double ins = cfg.insurance_rate_pct * 0.01 * C;
+    const double rr = 1.0 / (1.0 + nom);
+    const double wo_base = bc_year_bill(t, lds, PH, 1.0, false, cfg.nm_yearend_sell_rate);
+    BcPoint a;
+    a.w1 = 0.0;
+    a.wo1 = 0.0;
+    a.life = 0.0;
+    double balance = debt, acc = 0.0, df = rr, cum = -C, pb = 1e99;
+    bool paid = false;
+    double r_y = 1.0, s_y = 1.0, o_y = 1.0;       // pow_seq's running products
+    for (int y = 1; y <= N; y++) {
+        const double w = bc_year_bill(t, lds, PH, s_y, true, cfg.nm_yearend_sell_rate) * r_y;
+        const double wo = wo_base * r_y;
+        const double ev = (wo - w) + vor;           // ff:275
+        if (y == 1) {
+            a.w1 = w;
+            a.wo1 = wo;
+        }
+        a.life += ev;
+        const double oe = ins * o_y;
+        double interest = 0.0, payment = 0.0;
+        if (y <= term && pmt != 0.0) {
+            interest = balance * r;
+            payment = pmt;
+            balance = balance - (pmt - interest);
+        }
+        const double itc_y = (y == 1) ? itc : 0.0;
+        double sta_tax = 0.0, fed_tax = 0.0;
+        if (market != 0) {
+            const double dep = depr_frac(depr_type, y, cfg.depr_sl_years) * basis;
+            sta_tax = sta * (ev - oe - interest - dep);
+            fed_tax = fed * (ev - oe - interest - dep - sta_tax);
+        }
+        const double taxsav = itc_y - sta_tax - fed_tax;
+        const double atcf = ev - oe - payment + taxsav;
+        const double cfp = ev - oe + taxsav;
+        acc += atcf * df;
+        df *= rr;
+        cum += cfp;
+        if (!paid && cum > 0.0) {
+            pb = (cfp != 0.0) ? (double)y - cum / cfp : (double)y - 0.5;
+            paid = true;
+        }
+        r_y = r_y * rate_base;
+        s_y = s_y * sys_base;
+        o_y = o_y * (1.0 + infl);
+    }
+    a.npv = -(C - debt) + acc;
+    a.payback = pb;
+    a.cost = C;
+    a.bank = bank;
+    a.power = power;
+    a.tariff = tariff;
+    a.switched = switched;
+    a.status = st & (DGEN_ST_EMPTY_EC | DGEN_ST_ZERO_LOAD | DGEN_ST_DEMAND);
+    bc_store(S, o, a);
+}
 #endif  // !DGEN_TU_SEARCH
 
 }  // namespace
@@ -8789,6 +9124,60 @@ int32_t dgen_bill_months(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A
     else
         hipLaunchKernelGGL((k_bill_months<false>), dim3((unsigned)blocks), dim3(BM_BLOCK), lds, (hipStream_t)stream,
                            *T, *A, c->cfg, kw, tariff, n, dc_nq, *out);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_batt_curve(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const dgen_outputs* O,
+                        int64_t n, int32_t K, const double* kwh, const double* kw_pts,
+                        const dgen_batt_curve_out* out, void* stream) {
+    if (!c || !T || !A || !O || !kwh || !out || n < 0) {
+        set_err("dgen_batt_curve: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (K < 1 || K > DGEN_BATT_CURVE_MAX_POINTS) {
+        set_err("dgen_batt_curve: K = %d points, must be 1 .. %d", (int)K, DGEN_BATT_CURVE_MAX_POINTS);
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand) || (T->n_switches > 0 && !T->switches)) {
+        set_err("dgen_batt_curve: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    const void* cols[] = {A->load_row, A->cf_row, A->load_kwh, A->flags, A->sw_storage_off, A->sw_storage_cnt,
+                          A->econ_life, A->loan_term, A->inflation, A->pv_deg, A->escalator, A->down_payment,
+                          A->tax_rate, A->real_discount, A->itc_frac, A->capex, A->capex_combined,
+                          A->batt_capex_kwh, A->ccm, A->vor};
+    for (const void* p : cols)
+        if (!p) { set_err("dgen_batt_curve: missing agent column"); return DGEN_E_ARG; }
+    if (!O->system_kw || !O->status || !O->tariff_final || !O->switched) {
+        set_err("dgen_batt_curve: missing output column (system_kw, tariff_final, switched, status of the "
+                "sizing call)");
+        return DGEN_E_ARG;
+    }
+    if (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1) {
+        set_err("dgen_batt_curve: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not replayed: the daily plan under constant efficiencies only");
+        return DGEN_E_ARG;
+    }
+    const int64_t blocks = (n * K + BC_BLOCK - 1) / BC_BLOCK;
+    if (blocks > 0x7fffffff) {
+        set_err("dgen_batt_curve: K x n = %lld exceeds the launch grid", (long long)(n * K));
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    const size_t lds = (size_t)BC_PLANES * lds_half(T->max_periods) * BC_BLOCK * sizeof(double);
+    HIP_TRY(hipSetDevice(c->device));
+    if (lds > (size_t)c->lds_max) {
+        set_err("dgen_batt_curve: %zu B of LDS for %d periods exceed the device's %d B per block", lds,
+                lds_half(T->max_periods), c->lds_max);
+        return DGEN_E_ARG;
+    }
+    if (lds > 65536)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batt_curve),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_batt_curve, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A, *O,
+                       c->cfg, n, (int)K, c->battery, kwh, kw_pts, *out);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

@@ -761,6 +761,53 @@ class Engine:
         self._keep["_bill_kw"] = (k, t)       # alive until the next call (stream order)
         return res
 
+    def batt_curve(self, batch: AgentBatch, outputs, kwh, kw=None, want=None) -> Dict[str, object]:
+        """With-battery economics of `batch`, already sized or evaluated into
+        `outputs` (the alloc_outputs dict, or its c_outputs; system_kw,
+        tariff_final, switched and status are read, nothing is written), at K
+        caller-given banks per agent -- dgen_batt_curve, async on the current
+        stream.  kwh: [K, n] desired bank sizes in kWh (a device tensor or a
+        host array; [n] is one point), in the batch's device order (batch.perm
+        maps caller rows to it); 0 is a valid point (no bank).  kw: [K, n]
+        desired powers in kW, or None for the reference's 2-hour bank
+        (kwh / 2).  want: the members to compute (default all of
+        _lib.BATT_CURVE_FIELDS).  Returns {member: [K, n] device tensor}: npv,
+        payback_raw, total_cost, bank_kwh, power_kw, bill_w_year1,
+        bill_wo_year1, lifetime_savings (float64), tariff, switched, status
+        (int32; a point with a fatal status holds NaN).  The definitions are in
+        include/dgen_hip.h."""
+        torch = _torch()
+        want = tuple(_lib.BATT_CURVE_FIELDS if want is None else want)
+        bad = [k for k in want if k not in _lib.BATT_CURVE_FIELDS]
+        if bad or not want:
+            raise ValueError(f"batt_curve: want must name members of {_lib.BATT_CURVE_FIELDS} (got {want})")
+        n = batch.n
+        e = self._to_dev(kwh, torch.float64)
+        if e.dim() == 1:
+            e = e.view(1, -1)
+        e = e.contiguous()
+        p = None
+        if kw is not None:
+            p = self._to_dev(kw, torch.float64)
+            if p.dim() == 1:
+                p = p.view(1, -1)
+            p = p.contiguous()
+        if e.dim() != 2 or e.shape[1] != n or (p is not None and p.shape != e.shape):
+            raise ValueError(f"batt_curve: kwh (and kw) must be [K, {n}], got {tuple(e.shape)}"
+                             + ("" if p is None else f" and {tuple(p.shape)}"))
+        K = int(e.shape[0])
+        co = outputs if isinstance(outputs, _lib.Outputs) else self.c_outputs(outputs)
+        res = {k: torch.empty((K, n), dtype=torch.float64 if k in _lib.BATT_CURVE_F64 else torch.int32,
+                              device=self.dev) for k in want}
+        if n == 0 and 1 <= K <= _lib.BATT_CURVE_MAX_POINTS:
+            return res
+        bo = _lib.BattCurveOut(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(self.lib.dgen_batt_curve(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                            ctypes.byref(co), n, K, _ptr(e), _ptr(p), ctypes.byref(bo),
+                                            self.stream_handle()), "dgen_batt_curve")
+        self._keep["_batt_curve"] = (e, p)    # alive until the next call (stream order)
+        return res
+
     def brent_selftest(self, lo, hi, xatol, c2, x0, c1, maxn=64):
         torch = _torch()
         f = lambda v: self._to_dev(np.asarray(v, dtype=np.float64), torch.float64)

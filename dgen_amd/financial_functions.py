@@ -236,7 +236,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                 hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
                 keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
-                bill_metrics: bool = False):
+                bill_metrics: bool = False, batt_sizing=None):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -255,7 +255,9 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     batt_metrics: each sub-batch also summarises its battery dispatch on the
     device (batt_metrics.COLUMNS, per-agent values: the bits of one call).
     bill_metrics: each sub-batch also bills its three cases month by month on
-    the device (bill_metrics.COLUMNS, per-agent values: the bits of one call)."""
+    the device (bill_metrics.COLUMNS, per-agent values: the bits of one call).
+    batt_sizing: each sub-batch also runs the battery size what-if on the
+    device (batt_sizing.COLUMNS, per-agent values: the bits of one call)."""
     n = len(cols["load_kwh"])
     if max_rows is None:
         max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics, bill_metrics=bill_metrics)
@@ -263,7 +265,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     import torch
     try:
         return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
-                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -273,16 +275,16 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
         torch.cuda.empty_cache()
         return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
                            grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw,
-                           batt_metrics=batt_metrics, bill_metrics=bill_metrics)
+                           batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing)
 
 
 def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
                      grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None,
-                     batt_metrics: bool = False, bill_metrics: bool = False):
+                     batt_metrics: bool = False, bill_metrics: bool = False, batt_sizing=None):
     n = len(cols["load_kwh"])
     if n <= max_rows:
         return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
-                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -299,7 +301,8 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         parts.append(_run_device_once(b, sub, src, tm, nw, hourly_async=True, hourly_device=False,
                                       grid_metrics=grid_metrics, keep_planes=keep_planes,
                                       fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi],
-                                      batt_metrics=batt_metrics, bill_metrics=bill_metrics))
+                                      batt_metrics=batt_metrics, bill_metrics=bill_metrics,
+                                      batt_sizing=batt_sizing))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -318,6 +321,10 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
     if bill_metrics:
         from .bill_metrics import COLUMNS as BILL_COLUMNS
         for name in BILL_COLUMNS:
+            o[name] = np.concatenate([p[name] for p in parts])
+    if batt_sizing is not None:
+        from .batt_sizing import COLUMNS as SIZING_COLUMNS
+        for name in SIZING_COLUMNS:
             o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
         if not keep_planes:
@@ -342,7 +349,7 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                      hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True,
                      fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
-                     bill_metrics: bool = False):
+                     bill_metrics: bool = False, batt_sizing=None):
     """Size the batch in one device call (fixed_kw: evaluate caller row i at
     fixed_kw[i] kW instead, Engine.evaluate); net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
@@ -356,7 +363,9 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     batt_metrics: o also holds batt_metrics.COLUMNS, the annual battery
     dispatch summary of the sized batch (Engine.batt_summary, caller order).
     bill_metrics: o also holds bill_metrics.COLUMNS, the annual bill breakdown
-    of the three cases under tariff_final (Engine.bill_months, caller order)."""
+    of the three cases under tariff_final (Engine.bill_months, caller order).
+    batt_sizing: o also holds batt_sizing.COLUMNS, the best of the spec's
+    battery banks per agent (Engine.batt_curve, caller order)."""
     import time
     import torch
     from .attachment import state_hourly
@@ -390,6 +399,10 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     if bill_metrics:
         from .bill_metrics import annual_columns as bill_columns
         blm = bill_columns(eng, batch, out)
+    bsz = None
+    if batt_sizing is not None:
+        from .batt_sizing import annual_columns as sizing_columns
+        bsz = sizing_columns(eng, batch, out, batt_sizing)
     gm = None
     if grid_metrics:
         from .grid_metrics import annual_columns
@@ -419,6 +432,8 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         o.update(bm)
     if blm is not None:
         o.update(blm)
+    if bsz is not None:
+        o.update(bsz)
     if timing is not None:
         timing.update(upload_s=t1 - t0, device_s=t2 - t1, download_s=time.perf_counter() - t2)
     return o
@@ -553,7 +568,7 @@ def _fixed_kw_values(df: pd.DataFrame, fixed_kw) -> np.ndarray:
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
                grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
-               bill_metrics: bool = False):
+               bill_metrics: bool = False, batt_sizing=None):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -609,7 +624,17 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     same bits in every hourly mode and sub-batching.  All three cases are
     billed under tariff_final, the sticky tariff after both runs: the pvonly
     columns therefore reproduce first_year_elec_bill_with_system only where
-    the storage rate switch did not move the tariff."""
+    the storage rate switch did not move the tariff.  batt_sizing: a points
+    spec -- True, a (pv_to_batt ratios, hours) pair or a dict with those keys
+    (batt_sizing.grid) -- adds the seven columns batt_sizing.COLUMNS: the
+    with-battery run of every agent at each bank kW* / ratio kWh of each
+    duration (Engine.batt_curve, dgen_batt_curve) after each sub-batch's sizing
+    or evaluation, with the reference's point (0.8, 2 h) always appended, and
+    per agent the valid point of largest NPV: batt_opt_kwh, batt_opt_kw (the
+    installed bank), batt_opt_npv, batt_opt_payback, batt_opt_point (-1: none),
+    batt_opt_npv_gain (over the reference's point) and batt_opt_status.  No
+    plane is read: the same bits in every hourly mode and sub-batching.  None
+    (the default) leaves the frame unchanged."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
@@ -624,7 +649,7 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     o = _run_device(b, cols, src, dev_t, net_weights, hourly_async=hourly in ("lazy", "array", "list"),
                     hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
                     keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed,
-                    batt_metrics=batt_metrics, bill_metrics=bill_metrics)
+                    batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing)
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -701,6 +726,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
         from .bill_metrics import COLUMNS as BILL_COLUMNS
         for name in BILL_COLUMNS:
             out[name] = o[name]
+    if batt_sizing is not None:
+        from .batt_sizing import COLUMNS as SIZING_COLUMNS
+        for name in SIZING_COLUMNS:
+            out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:
         # download_wait_s: time the frame assembly waited for the hourly planes
@@ -712,14 +741,15 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
                hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
                grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
-               bill_metrics: bool = False):
+               bill_metrics: bool = False, batt_sizing=None):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
     agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
     grid_metrics: size_frame's 18 per-agent grid-exchange columns.  fixed_kw:
     size_frame's (a column name or an aligned array: the chunk's agents are
     evaluated at those sizes instead of being sized).  batt_metrics:
     size_frame's per-agent battery dispatch columns (batt_diag_*).
-    bill_metrics: size_frame's 18 per-agent year-1 bill columns (bill_*)."""
+    bill_metrics: size_frame's 18 per-agent year-1 bill columns (bill_*).
+    batt_sizing: size_frame's points spec (the seven batt_opt_* columns)."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -733,7 +763,8 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     # kernel's fixed-order tree agree to rounding (parity test: 1e-12 relative)
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
                            net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics,
-                           fixed_kw=fixed_kw, batt_metrics=batt_metrics, bill_metrics=bill_metrics)
+                           fixed_kw=fixed_kw, batt_metrics=batt_metrics, bill_metrics=bill_metrics,
+                           batt_sizing=batt_sizing)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

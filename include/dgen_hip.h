@@ -68,6 +68,9 @@ extern "C" {
 #define DGEN_ST_ZERO_LOAD    0x40  /* load_kwh == 0: reference divides by zero (ff:549)*/
 #define DGEN_ST_DEMAND       0x80  /* demand-charge mat outside SSC's / the record's   */
                                    /* limits (month, period, tier numbering)          */
+#define DGEN_ST_HOURLY_FORM  0x100 /* dgen_batt_curve only (no other entry sets it):  */
+                                   /* the point's tariff bills hourly imports, demand  */
+                                   /* charges or kWh/kW tiers, which it does not cover */
 
 /* Engine configuration: the PySAM config defaults the reference never sets
  * (CustomGenerationBattery{Residential,Commercial}, ff:59-80) plus the
@@ -952,6 +955,73 @@ typedef struct {   /* each [12][n] month-major, any may be NULL, except status [
 int32_t dgen_bill_months(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
                          const double* kw, const int32_t* tariff, int64_t n, const dgen_bill_opt* opt,
                          const dgen_bill_out* out, void* stream);
+
+/* Battery size what-if (additive to ABI 14): the with-battery economics of a
+ * batch dgen_size_agents or dgen_eval_agents already sized (`sized`: its
+ * system_kw, tariff_final, switched and status are read, nothing is written) at
+ * K caller-given banks per agent.  A point is one more
+ * calc_system_performance(kW*, en_batt=True) on the agent as the sizing call
+ * left it (oracle/orc.c, the PV+battery run of size_agent_impl) with the
+ * battery's desired kWh and kW supplied instead of kW* / 0.8 and kW* / 0.8 / 2.
+ * kwh: [K][n] device doubles, point-major (point k of agent i at [k x n + i]);
+ * kw_pts: [K][n] or NULL (then desired_kw = desired_kwh / 2.0, the reference's
+ * 2-hour bank).  One lane per (agent, point); per point, with kW* = system_kw:
+ *   bank, power = battery_model_sizing(desired_kw, desired_kwh, 240 V
+ *       residential | 500 V) as the scan sizes it (a positive desired_kwh below
+ *       half a string still buys one string); 0, 0 for desired_kwh = 0 (a valid
+ *       point: no bank) and after dgen_set_battery(0)
+ *   dispatch: dgen_batt_summary's replay (ls, cs6 at kW*, the day's plan, the
+ *       month floor, the scan's hour) -> the system output sys[h]
+ *   storage rate switch, when bank > 0: exactly one of the agent's sw_storage
+ *       rows with min_kw <= bank < max_kw moves the point to that row's tariff
+ *       (switched = 1, otc = its one-time charge); otherwise the point keeps
+ *       the tariff_final and switched it was handed and otc = 0 (the sticky,
+ *       in-place semantics of elec.py:838-863)
+ *   bins, per (month, period) of that tariff's energy schedule, fp64
+ *       sequential in hour order: lbin = sum ld, gbin = sum sys
+ *   years y = 1 .. N (economic life): s_y = (1 - pv_deg)^(y-1), r_y = (1 +
+ *       inflation + escalator)^(y-1), sequential products; bill_w[y] = r_y x
+ *       year_bill at net bins lbin - s_y x gbin (mo 4: load lbin, generation
+ *       s_y x gbin), bill_wo[y] = r_y x year_bill at lbin alone (year_bill and
+ *       month_energy_charge as under dgen_bill_months, fixed charge and the
+ *       December true-up included); aev[y] = (bill_wo[y] - bill_w[y]) + vor
+ *   cost = ((kW* > 0 ? capex_combined : capex) x kW* + batt_capex_kwh x bank x
+ *       0.7) x ccm + otc
+ *   Cashloan as the sizing call's (loan_inputs, orc_cashloan); payback_raw by
+ *       its chain (1e99: none); npv = atcf[0] + sum_y atcf[y] x rr^y added in
+ *       year order with rr^y a running product (the oracle's Horner chain to
+ *       rounding)
+ * Members, each [K][n] point-major, any may be NULL (a NULL member is not
+ * written): npv, payback_raw, total_cost (cost), bank_kwh, power_kw,
+ * bill_w_year1, bill_wo_year1, lifetime_savings (sum of aev[y], y = 1 .. N, in
+ * year order), tariff and switched (after the switch), status.
+ * Covered: tariffs that bill from bins -- metering options 0, 1 and 4, tier
+ * units 0 and 2, no demand charge billed.  A point whose tariff after the
+ * switch bills hourly imports (options 2, 3), carries billed demand charges or
+ * has kWh/kW tier units gets DGEN_ST_HOURLY_FORM, as does every point of a
+ * DGEN_ST_UNIT agent.  A point whose kwh is not finite or is negative, or whose
+ * kw_pts is not finite or not positive while kwh > 0, gets DGEN_ST_BOUNDS.  An
+ * agent the sizing call flagged DGEN_ST_BOUNDS, _TARIFF or _YEARS keeps that
+ * status in every point.  A switch to an index outside the table, or to a
+ * tariff beyond tables->max_periods, gets DGEN_ST_TARIFF.  Every double member
+ * of such a point is NaN; other points carry the agent's informational bits
+ * (DGEN_ST_EMPTY_EC, _ZERO_LOAD, _DEMAND) or 0.  Points are independent:
+ * column k of a K-point call is the K = 1 call at that point bit for bit.  No
+ * atomics and no cross-lane sums: run-to-run identical.  No workspace.
+ * 1 <= K <= DGEN_BATT_CURVE_MAX_POINTS, else DGEN_E_ARG; batt_update_hours == 1
+ * or batt_loss_model == 1 returns DGEN_E_ARG, as in dgen_batt_summary.  The
+ * kernel keeps 26 x max_periods x 512 B of LDS per 64 points.                 */
+#define DGEN_BATT_CURVE_MAX_POINTS 16
+
+typedef struct {            /* each [K][n], point-major; any may be NULL */
+    double  *npv, *payback_raw, *total_cost, *bank_kwh, *power_kw,
+            *bill_w_year1, *bill_wo_year1, *lifetime_savings;   /* sum_y aev[y], y = 1..N */
+    int32_t *tariff, *switched, *status;
+} dgen_batt_curve_out;
+
+int32_t dgen_batt_curve(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                        const dgen_outputs* sized, int64_t n, int32_t K, const double* kwh,
+                        const double* kw_pts, const dgen_batt_curve_out* out, void* stream);
 
 #ifdef __cplusplus
 }
