@@ -167,6 +167,14 @@ class BattCurveOut(ctypes.Structure):
     _fields_ = [(name, _vp) for name in BATT_CURVE_FIELDS]
 
 
+NB_CAPM = 192   # include/dgen_hip.h DGEN_NB_CAPM
+
+
+class BattNetOpt(ctypes.Structure):
+    """dgen_batt_net_opt: cap = the mixed hours a month's list holds per point (<= 0: NB_CAPM)."""
+    _fields_ = [("cap", _i32), ("pad", _i32)]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -185,7 +193,7 @@ EXPORTED = [
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
-    "dgen_bill_months", "dgen_batt_curve",
+    "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net",
 ]
 
 
@@ -280,6 +288,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_batt_curve.restype = _i32
     L.dgen_batt_curve.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
                                   _i64, _i32, _vp, _vp, ctypes.POINTER(BattCurveOut), _vp]
+    L.dgen_batt_curve_net.restype = _i32
+    L.dgen_batt_curve_net.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
+                                      _i64, _i32, _vp, _vp, ctypes.POINTER(BattNetOpt),
+                                      ctypes.POINTER(BattCurveOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

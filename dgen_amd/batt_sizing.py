@@ -13,9 +13,13 @@ This module carries that up:
     annual_columns(engine, batch, out, spec)     the per-agent columns of the drop-in switch
                                                  (financial_functions.size_frame(batt_sizing=spec))
 
-The kernel covers the tariffs that bill from monthly bins (metering options 0,
-1, 4; tier units 0, 2; no billed demand charge); a point under another form
-carries _lib.ST_HOURLY_FORM and NaN, and is never a best point.
+dgen_batt_curve covers the tariffs that bill from monthly bins (metering
+options 0, 1, 4; tier units 0, 2; no billed demand charge); a point under
+another form carries _lib.ST_HOURLY_FORM and NaN, and is never a best point.
+net=True (the spec key "net_billing": True) adds dgen_batt_curve_net on the
+same buffers: the net-billing tariffs (options 2 and 3, the TS sell rate
+included) are computed too, and what stays flagged is kWh/kW tier units and
+billed demand charges.
 """
 from __future__ import annotations
 
@@ -75,10 +79,12 @@ def _inverse(engine, perm):
     return engine._to_dev(iv, torch.int64)
 
 
-def curve_outputs(engine, batch, out, kwh, kw=None, want: Optional[Sequence[str]] = None) -> Dict[str, object]:
+def curve_outputs(engine, batch, out, kwh, kw=None, want: Optional[Sequence[str]] = None,
+                  net: bool = False, net_cap: Optional[int] = None) -> Dict[str, object]:
     """Engine.batt_curve of a batch sized (or evaluated) into `out`, with kwh /
     kw given and the members returned in caller order (batch.perm):
-    {member: [K, n] device tensor}."""
+    {member: [K, n] device tensor}.  net / net_cap: Engine.batt_curve's (the
+    net-billing points computed too)."""
     import torch
     e = engine._to_dev(kwh, torch.float64)
     p = None if kw is None else engine._to_dev(kw, torch.float64)
@@ -86,11 +92,19 @@ def curve_outputs(engine, batch, out, kwh, kw=None, want: Optional[Sequence[str]
         pm = engine._to_dev(np.asarray(batch.perm, np.int64), torch.int64)
         e = e.index_select(e.dim() - 1, pm)
         p = None if p is None else p.index_select(p.dim() - 1, pm)
-    d = engine.batt_curve(batch, out, e, p, want)
+    d = engine.batt_curve(batch, out, e, p, want, **_net_kw(net, net_cap))
     inv = _inverse(engine, batch.perm)
     if inv is None:
         return d
     return {k: v.index_select(1, inv) for k, v in d.items()}
+
+
+def _net_kw(net, net_cap=None):
+    """Engine.batt_curve's keywords; none without net, so that a caller's
+    engine sees the call it always saw."""
+    if not net:
+        return {}
+    return {"net": True} if net_cap is None else {"net": True, "net_cap": net_cap}
 
 
 def best_point(curve: Dict[str, object]):
@@ -152,11 +166,12 @@ def summarize(curve: Dict[str, object], ref_point: int) -> Dict[str, object]:
 
 def grid(spec) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
     """size_frame's batt_sizing spec as (pv_to_batt, hours): a dict with either
-    key, a (pv_to_batt, hours) pair, or True for the default grid."""
+    key, a (pv_to_batt, hours) pair, or True for the default grid.  The dict's
+    "net_billing" key is not part of the grid (net_billing(spec))."""
     if spec is True:
         return (0.4, 0.8, 1.6), (1.0, 2.0, 4.0)
     if isinstance(spec, dict):
-        bad = set(spec) - {"pv_to_batt", "hours"}
+        bad = set(spec) - {"pv_to_batt", "hours", "net_billing"}
         if bad:
             raise ValueError(f"batt_sizing: unknown keys {sorted(bad)}")
         return tuple(spec.get("pv_to_batt", (REF_PV_TO_BATT,))), tuple(spec.get("hours", (REF_HOURS,)))
@@ -164,12 +179,20 @@ def grid(spec) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
     return tuple(r), tuple(h)
 
 
+def net_billing(spec) -> bool:
+    """True when the spec asks for the net-billing tariffs too: a dict with
+    "net_billing": True."""
+    return isinstance(spec, dict) and bool(spec.get("net_billing", False))
+
+
 def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     """The drop-in switch's per-agent columns (COLUMNS) of a sized output dict
     as host arrays in caller order: the curve over ratio_points(system_kw,
     *grid(spec)) with the reference's point (0.8, 2.0) appended as the last
     point, reduced by summarize().  float64, except batt_opt_point and
-    batt_opt_status (int64).  Only these [n] vectors cross to the host."""
+    batt_opt_status (int64).  Only these [n] vectors cross to the host.  With
+    "net_billing": True in the spec the net-billing points are computed too
+    (dgen_batt_curve_net)."""
     import torch
     r, h = grid(spec)
     skw = out["system_kw"]
@@ -180,7 +203,8 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
         raise ValueError(f"batt_sizing: {kwh.shape[0]} points (the reference's included) exceed "
                          f"{_lib.BATT_CURVE_MAX_POINTS}")
     # an unsized agent's system_kw may be NaN: its points are flagged, not read
-    d = engine.batt_curve(batch, out, kwh, kw, ("npv", "payback_raw", "bank_kwh", "power_kw", "status"))
+    d = engine.batt_curve(batch, out, kwh, kw, ("npv", "payback_raw", "bank_kwh", "power_kw", "status"),
+                          **_net_kw(net_billing(spec)))
     s = summarize(d, int(kwh.shape[0]) - 1)
     inv = _inverse(engine, batch.perm)
     res = {}

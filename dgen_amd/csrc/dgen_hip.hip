@@ -7556,6 +7556,376 @@ k_batt_curve(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t
     a.status = st & (DGEN_ST_EMPTY_EC | DGEN_ST_ZERO_LOAD | DGEN_ST_DEMAND);
     bc_store(S, o, a);
 }
+
+// ---------------------------------------------------------------------------
+// Battery size what-if under net billing (dgen_batt_curve_net; the definition
+// is in include/dgen_hip.h): the points k_batt_curve flags because their
+// tariff bills hourly imports (metering options 2 and 3).  One lane per
+// (agent, point) as there, the same year walk; the blocks are persistent
+// (grid-stride over the 64-point tiles), so the per-lane workspace is sized by
+// the launch, not by K x n.  The hourly bill of year y needs each hour's sign
+// at s_y: the lane splits the hours with the scan's rule (NB_SYS_ZERO_IMPORT
+// above) over [s_N, 1] -- an hour importing at both ends adds to two sums per
+// (month, period), linear in s; an hour exporting at both ends to two more,
+// times the hour's sell weight; any other hour goes to the month's mixed list.
+// At each month's end the lane bills the month for every year from the sums
+// at s_y plus the mixed hours, into per-year accumulators.  Options 2 and 3
+// carry nothing but the dollar carry across months, so LDS holds one month:
+// [plane][period][lane] doubles, planes lbin, SA_L, SA_g, SX_gw, SX_Lw and the
+// year's imp and exv.  Workspace per block: [2 MAXY][lane] doubles (bill_w[y],
+// carry[y]) and [cap][lane] 16-B mixed entries.  A lane stores entry k only
+// for k < cap, the capacity the workspace was sized for; a month beyond it
+// ends the lane with nothing written.  No atomics, no cross-lane traffic.
+// ---------------------------------------------------------------------------
+constexpr int BN_PLANES = 7;
+struct BnEnt {
+    double g;             // the hour's system output
+    float sh;             // its float32 shape value: load = sh x ls, as the walk formed it
+    uint32_t hp;          // hour << 8 | period
+};
+static_assert(sizeof(BnEnt) == 16, "16-B mixed-hour entries");
+constexpr size_t BN_ACC_BYTES = (size_t)2 * MAXY * BC_BLOCK * sizeof(double);
+__host__ __device__ inline size_t bn_block_bytes(int cap) {
+    return BN_ACC_BYTES + (size_t)cap * BC_BLOCK * sizeof(BnEnt);
+}
+
+// month_energy_charge (units 0 and 2) of the lane's u plane; U = sum_p u[p]
+__device__ double bn_energy_charge(const dgen_tariff& t, int m, const double* u, double U) {
+    const int P = t.P, NT = t.T;
+    double ec = 0.0;
+    if (U > 0.0) {
+        if (NT == 1) {
+            for (int p = 0; p < P; p++) ec += u[p * BC_BLOCK] * t.buy[p][0];
+        } else {
+            const double scale = (t.unit == 2) ? (double)c_days_in_month[m] : 1.0;
+            double prev = 0.0;
+            for (int k = 0; k < NT; k++) {
+                const double hi = (k == NT - 1) ? INFINITY : t.cap[k] * scale;
+                const double top = U < hi ? U : hi;
+                double amt = top - prev;
+                if (amt < 0.0) amt = 0.0;
+                if (hi > prev) prev = hi;
+                for (int p = 0; p < P; p++) ec += (u[p * BC_BLOCK] / U) * amt * t.buy[p][k];
+            }
+        }
+    }
+    return ec;
+}
+
+// one (agent, point); lds: the lane's column, accw / ent: the lane's workspace columns
+__device__ void bn_point(const dgen_tables& T, const dgen_agents& A, const dgen_outputs& O, const dgen_cfg& cfg,
+                         int64_t n, int64_t o, int batt_on, const double* __restrict__ kwh_pts,
+                         const double* __restrict__ kw_pts, const dgen_batt_curve_out& S, double* lds, int PH,
+                         double* accw, BnEnt* ent, int cap) {
+    const int64_t i = o % n;
+    const int st = O.status[i];
+    int tariff = O.tariff_final[i], switched = O.switched[i];
+    // what dgen_batt_curve flags for another reason than the tariff's form stays its own
+    if (st & (DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_YEARS | DGEN_ST_UNIT)) return;
+    const double desired_kwh = kwh_pts[o];
+    const double desired_kw = kw_pts ? kw_pts[o] : desired_kwh / 2.0;
+    if (!(desired_kwh >= 0.0) || isinf(desired_kwh)) return;
+    if (kw_pts && desired_kwh > 0.0 && (!(desired_kw > 0.0) || isinf(desired_kw))) return;
+    const int N = A.econ_life[i];
+    if (N < 1 || N > MAXY) return;
+    if (tariff < 0 || tariff >= T.n_tariffs) return;
+    const uint8_t aflags = A.flags[i];
+    const bool is_res = (aflags & 1) != 0;
+    const double kw_star = O.system_kw[i];
+    double bank = 0.0, power = 0.0;
+    if (batt_on) batt_size(desired_kw, desired_kwh, is_res ? 240.0 : 500.0, cfg, &bank, &power);
+    double otc = 0.0;
+    if (bank > 0.0) {       // the storage rate switch, sticky on the state the sizing call left
+        int nt = -1;
+        otc = rate_switch(T.switches + A.sw_storage_off[i], A.sw_storage_cnt[i], bank, &nt);
+        if (nt != -1) {
+            tariff = nt;
+            switched = 1;
+        }
+    }
+    if (tariff < 0 || tariff >= T.n_tariffs) return;
+    const dgen_tariff& t = T.tariffs[tariff];
+    const int P = t.P, mo = t.mo;
+    if (P < 1 || P > PH || t.T < 1 || t.T > MAXT) return;
+    if (!net_hourly(t) || peak_unit(t) || tariff_demand(T, cfg, t) != nullptr) return;
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double ls = A.load_kwh[i] / T.shape_sum[lr];
+    const double cs6 = (((kw_star * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    const char* const esch = reinterpret_cast<const char*>(t.wkday);
+    // TS sell rate (mo 2, not CA, a wholesale row): ts[h] = (double)(float)(wholesale[h] x price_mult)
+    const int wr = (A.wholesale_row && A.price_mult) ? A.wholesale_row[i] : -1;
+    const bool ts_on = mo == 2 && (aflags & 2) == 0 && wr >= 0 && T.wholesale != nullptr;
+    const bool wave_ts = __ballot(ts_on) != 0;
+    const double* __restrict__ tsp = ts_on ? T.wholesale + (int64_t)wr * NH : T.shape_sum + lr;
+    const int tstride = ts_on ? 1 : 0;
+    const double ts_mult = ts_on ? A.price_mult[i] : 1.0;
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    const double sys_base = 1.0 - (A.pv_deg[i] * 100.0) * 0.01;
+    const double sN = pow_seq(sys_base, N - 1);
+    const double s_lo = sN < 1.0 ? sN : 1.0, s_hi = sN > 1.0 ? sN : 1.0;
+    double* const pl_lb = lds;                                  // lbin
+    double* const pl_al = lds + (size_t)1 * PH * BC_BLOCK;      // SA_L
+    double* const pl_ag = lds + (size_t)2 * PH * BC_BLOCK;      // SA_g
+    double* const pl_xg = lds + (size_t)3 * PH * BC_BLOCK;      // SX_gw
+    double* const pl_xl = lds + (size_t)4 * PH * BC_BLOCK;      // SX_Lw
+    double* const pl_u = lds + (size_t)5 * PH * BC_BLOCK;       // the year's imp
+    double* const pl_x = lds + (size_t)6 * PH * BC_BLOCK;       // the year's exv
+    double soc = cfg.batt_init_soc;
+    double wo_base = 0.0, wo_carry = 0.0;
+    double tq[4] = {0.0, 0.0, 0.0, 0.0}, tn[4] = {0.0, 0.0, 0.0, 0.0};   // TS: this hour quad's rates, the next's
+    if (wave_ts) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) tq[j] = tsp[j * tstride];
+    }
+    BcDay cur, nxt;
+    bc_day_load(shp, cfp, esch, 0, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        for (int p = 0; p < P; p++) {
+            pl_lb[p * BC_BLOCK] = 0.0;
+            pl_al[p * BC_BLOCK] = 0.0;
+            pl_ag[p * BC_BLOCK] = 0.0;
+            pl_xg[p * BC_BLOCK] = 0.0;
+            pl_xl[p * BC_BLOCK] = 0.0;
+        }
+        int bcur = 0, n_m = 0;
+        double b_lb = 0.0, b_al = 0.0, b_ag = 0.0, b_xg = 0.0, b_xl = 0.0, mfloor = 0.0;
+        const int d_end = c_month_start_day[m + 1];
+        for (int d = c_month_start_day[m]; d < d_end; d++) {
+            {   // the next day's rows (December 31 loads itself again)
+                const int dn = d < 364 ? d + 1 : 364;
+                bc_day_load(shp, cfp, esch, dn, dn < d_end ? m : m + 1, nxt);
+            }
+            double dv[24];
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++)
+                dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+            sort24_desc(dv);
+            const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+            double target = day_target_sorted(dv, power, avail0);
+            {   // dgen_cfg.batt_month_floor: the month's target never falls
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+            const int h0 = d * 24;
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                if ((hh & 3) == 0 && wave_ts) {        // wave-uniform
+                    const int hn = h0 + hh + 4 <= NH - 4 ? h0 + hh + 4 : NH - 4;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) tn[j] = tsp[(hn + j) * tstride];
+                }
+                const float sh = opaque_f(cur.s[hh >> 2][hh & 3]);
+                const double ld = (double)sh * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                const HourStep hs = batt_hour(ld - pv, pv, target, power, bank, soc, cfg, inv_eta_in, in_per_bank,
+                                              out_per_bank);
+                int p = (int)((cur.e[hh >> 3] >> (8 * (hh & 7))) & 0xffu);
+                p = p < P ? p : P - 1;                  // a schedule beyond P: never past the lane's bins
+                if (p != bcur) {
+                    pl_lb[bcur * BC_BLOCK] = b_lb;
+                    pl_al[bcur * BC_BLOCK] = b_al;
+                    pl_ag[bcur * BC_BLOCK] = b_ag;
+                    pl_xg[bcur * BC_BLOCK] = b_xg;
+                    pl_xl[bcur * BC_BLOCK] = b_xl;
+                    bcur = p;
+                    b_lb = pl_lb[p * BC_BLOCK];
+                    b_al = pl_al[p * BC_BLOCK];
+                    b_ag = pl_ag[p * BC_BLOCK];
+                    b_xg = pl_xg[p * BC_BLOCK];
+                    b_xl = pl_xl[p * BC_BLOCK];
+                }
+                const double gk = hs.sys;
+                const double wd = ts_on ? (double)(float)(tq[hh & 3] * ts_mult) : 1.0;
+                const double vlo = ld - gk * s_lo, vhi = ld - gk * s_hi;
+                const double slack = 1e-10 * (fabs(ld) + fabs(gk) * s_hi);
+                const bool imp = fmin(vlo, vhi) > -slack;              // imports (or ~0) at every s
+                const bool exq = !imp && fmax(vlo, vhi) < -slack;      // exports at every s
+                b_lb += ld;
+                b_al += imp ? ld : 0.0;
+                b_ag += imp ? gk : 0.0;
+                b_xg += exq ? gk * wd : 0.0;
+                b_xl += exq ? ld * wd : 0.0;
+                if (!imp && !exq) {
+                    if (n_m < cap) {                    // cap: the entries the workspace holds per lane
+                        BnEnt e;
+                        e.g = gk;
+                        e.sh = sh;
+                        e.hp = ((uint32_t)(h0 + hh) << 8) | (uint32_t)p;
+                        ent[(size_t)n_m * BC_BLOCK] = e;
+                    }
+                    n_m++;
+                }
+                if ((hh & 3) == 3) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) tq[j] = tn[j];
+                }
+            }
+            cur = nxt;
+        }
+        if (n_m > cap) return;                  // the month's mixed list overflowed: the point is not computed
+        pl_lb[bcur * BC_BLOCK] = b_lb;
+        pl_al[bcur * BC_BLOCK] = b_al;
+        pl_ag[bcur * BC_BLOCK] = b_ag;
+        pl_xg[bcur * BC_BLOCK] = b_xg;
+        pl_xl[bcur * BC_BLOCK] = b_xl;
+        {   // the no-system month: imp = lbin, no credit
+            double U = 0.0;
+            for (int p = 0; p < P; p++) U += pl_lb[p * BC_BLOCK];
+            const double charge = bn_energy_charge(t, m, pl_lb, U);
+            double bill = t.fixed;
+            if (mo == 3) {
+                const double e = charge - 0.0 - wo_carry;
+                wo_carry = e < 0.0 ? -e : 0.0;
+                bill += e < 0.0 ? 0.0 : e;
+            } else {
+                bill += charge;
+                bill -= 0.0;
+            }
+            wo_base += bill;
+        }
+        double s_y = 1.0;
+        for (int y = 0; y < N; y++) {           // the month's bill of year y + 1
+            for (int p = 0; p < P; p++) {
+                pl_u[p * BC_BLOCK] = pl_al[p * BC_BLOCK] - s_y * pl_ag[p * BC_BLOCK];
+                pl_x[p * BC_BLOCK] = s_y * pl_xg[p * BC_BLOCK] - pl_xl[p * BC_BLOCK];
+            }
+            for (int k = 0; k < n_m; k++) {     // the mixed hours, in hour order
+                const BnEnt e = ent[(size_t)k * BC_BLOCK];
+                const int p = (int)(e.hp & 0xffu);
+                const double dd = (double)e.sh * ls - s_y * e.g;
+                if (dd > 0.0) {
+                    pl_u[p * BC_BLOCK] += dd;
+                } else {
+                    const double wd = ts_on ? (double)(float)(tsp[e.hp >> 8] * ts_mult) : 1.0;
+                    pl_x[p * BC_BLOCK] += (-dd) * wd;
+                }
+            }
+            double U = 0.0, crd = 0.0;
+            for (int p = 0; p < P; p++) U += pl_u[p * BC_BLOCK];
+            const double charge = bn_energy_charge(t, m, pl_u, U);
+            if (ts_on) {
+                for (int p = 0; p < P; p++) crd += pl_x[p * BC_BLOCK];
+            } else {
+                for (int p = 0; p < P; p++) crd += pl_x[p * BC_BLOCK] * t.sell[p][0];
+            }
+            double bill = t.fixed;
+            double carry = m == 0 ? 0.0 : accw[(size_t)(MAXY + y) * BC_BLOCK];
+            if (mo == 3) {
+                const double e = charge - crd - carry;
+                carry = e < 0.0 ? -e : 0.0;
+                bill += e < 0.0 ? 0.0 : e;
+            } else {
+                bill += charge;
+                bill -= crd;
+            }
+            accw[(size_t)(MAXY + y) * BC_BLOCK] = carry;
+            accw[(size_t)y * BC_BLOCK] = (m == 0 ? 0.0 : accw[(size_t)y * BC_BLOCK]) + bill;
+            s_y = s_y * sys_base;
+        }
+    }
+    // ---- the Cashloan (orc_cashloan) over the stored years, as k_batt_curve steps it ----
+    const double rate_base = 1.0 + (A.inflation[i] * 100.0) * 0.01 + (A.escalator[i] * 100.0) * 0.01;
+    const double vor = A.vor[i];
+    const double system_costs = (kw_star > 0.0) ? A.capex_combined[i] * kw_star : A.capex[i] * kw_star;
+    const double batt_costs = A.batt_capex_kwh[i] * bank * 0.7;
+    const double C = ((system_costs + batt_costs) * A.ccm[i]) + 0.0 + otc;
+    const int market = is_res ? 0 : 1, depr_type = is_res ? 0 : 2;
+    const double infl = (A.inflation[i] * 100.0) * 0.01;
+    const double real = (A.real_discount[i] * 100.0) * 0.01;
+    const double nom = (1.0 + real) * (1.0 + infl) - 1.0;
+    const double fed = ((A.tax_rate[i] * 100.0) * 0.7) * 0.01, sta = ((A.tax_rate[i] * 100.0) * 0.3) * 0.01;
+    const double debt = (100.0 - (A.down_payment[i] * 100.0)) * 0.01 * C;
+    const double r = cfg.loan_rate_pct * 0.01;
+    const int term = A.loan_term[i];
+    double pmt = 0.0;
+    if (term > 0 && debt != 0.0) {
+        if (r != 0.0) {
+            const double f = pow_seq(1.0 + r, term);
+            pmt = debt * r / (1.0 - 1.0 / f);
+        } else {
+            pmt = debt / (double)term;
+        }
+    }
+    double itc = A.itc_frac[i] * 0.01 * C;
+    if (itc > cfg.itc_fed_max) itc = cfg.itc_fed_max;
+    const double basis = C - 0.5 * itc;
+    const double ins = cfg.insurance_rate_pct * 0.01 * C;
+    const double rr = 1.0 / (1.0 + nom);
+    BcPoint a;
+    a.w1 = 0.0;
+    a.wo1 = 0.0;
+    a.life = 0.0;
+    double balance = debt, acc = 0.0, df = rr, cum = -C, pb = 1e99;
+    bool paid = false;
+    double r_y = 1.0, o_y = 1.0;                  // pow_seq's running products
+    for (int y = 1; y <= N; y++) {
+        const double w = accw[(size_t)(y - 1) * BC_BLOCK] * r_y;
+        const double wo = wo_base * r_y;
+        const double ev = (wo - w) + vor;           // ff:275
+        if (y == 1) {
+            a.w1 = w;
+            a.wo1 = wo;
+        }
+        a.life += ev;
+        const double oe = ins * o_y;
+        double interest = 0.0, payment = 0.0;
+        if (y <= term && pmt != 0.0) {
+            interest = balance * r;
+            payment = pmt;
+            balance = balance - (pmt - interest);
+        }
+        const double itc_y = (y == 1) ? itc : 0.0;
+        double sta_tax = 0.0, fed_tax = 0.0;
+        if (market != 0) {
+            const double dep = depr_frac(depr_type, y, cfg.depr_sl_years) * basis;
+            sta_tax = sta * (ev - oe - interest - dep);
+            fed_tax = fed * (ev - oe - interest - dep - sta_tax);
+        }
+        const double taxsav = itc_y - sta_tax - fed_tax;
+        const double atcf = ev - oe - payment + taxsav;
+        const double cfp = ev - oe + taxsav;
+        acc += atcf * df;
+        df *= rr;
+        cum += cfp;
+        if (!paid && cum > 0.0) {
+            pb = (cfp != 0.0) ? (double)y - cum / cfp : (double)y - 0.5;
+            paid = true;
+        }
+        r_y = r_y * rate_base;
+        o_y = o_y * (1.0 + infl);
+    }
+    a.npv = -(C - debt) + acc;
+    a.payback = pb;
+    a.cost = C;
+    a.bank = bank;
+    a.power = power;
+    a.tariff = tariff;
+    a.switched = switched;
+    a.status = st & (DGEN_ST_EMPTY_EC | DGEN_ST_ZERO_LOAD | DGEN_ST_DEMAND);
+    bc_store(S, o, a);
+}
+
+__global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_batt_curve_net(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t n, int K, int batt_on,
+                 const double* __restrict__ kwh_pts, const double* __restrict__ kw_pts, dgen_batt_curve_out S,
+                 char* __restrict__ ws, int cap) {
+    const int PH = lds_half(T.max_periods);
+    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BC_BLOCK]
+    char* const wsb = ws + (size_t)blockIdx.x * bn_block_bytes(cap);
+    double* const accw = reinterpret_cast<double*>(wsb) + threadIdx.x;
+    BnEnt* const ent = reinterpret_cast<BnEnt*>(wsb + BN_ACC_BYTES) + threadIdx.x;
+    const int64_t total = (int64_t)K * n, step = (int64_t)gridDim.x * BC_BLOCK;
+    for (int64_t o = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; o < total; o += step)
+        bn_point(T, A, O, cfg, n, o, batt_on, kwh_pts, kw_pts, S, lds, PH, accw, ent, cap);
+}
 #endif  // !DGEN_TU_SEARCH
 
 }  // namespace
@@ -7674,6 +8044,8 @@ struct dgen_ctx {
     int n_cu = 256;                // the device's compute units
     int ex_last_nch = 0;
     int64_t ex_last_off[MAXCH] = {0};
+    char* bn_ws = nullptr;         // dgen_batt_curve_net: [resident blocks][bn_block_bytes(cap)] (grown on demand)
+    size_t bn_ws_cap = 0;
 };
 
 static int fold_one(dgen_ctx* c, int slot) {
@@ -7835,6 +8207,7 @@ int32_t dgen_close(dgen_ctx* c) {
     if (c->ex_ws) (void)hipFree(c->ex_ws);
     if (c->ex_list) (void)hipFree(c->ex_list);
     if (c->ex_next) (void)hipFree(c->ex_next);
+    if (c->bn_ws) (void)hipFree(c->bn_ws);
     delete c;
     return DGEN_OK;
 }
@@ -9178,6 +9551,87 @@ int32_t dgen_batt_curve(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_batt_curve, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A, *O,
                        c->cfg, n, (int)K, c->battery, kwh, kw_pts, *out);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_batt_curve_net(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const dgen_outputs* O,
+                            int64_t n, int32_t K, const double* kwh, const double* kw_pts,
+                            const dgen_batt_net_opt* opt, const dgen_batt_curve_out* out, void* stream) {
+    if (!c || !T || !A || !O || !kwh || !out || n < 0) {
+        set_err("dgen_batt_curve_net: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (K < 1 || K > DGEN_BATT_CURVE_MAX_POINTS) {
+        set_err("dgen_batt_curve_net: K = %d points, must be 1 .. %d", (int)K, DGEN_BATT_CURVE_MAX_POINTS);
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand) || (T->n_switches > 0 && !T->switches)) {
+        set_err("dgen_batt_curve_net: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    const void* cols[] = {A->load_row, A->cf_row, A->load_kwh, A->flags, A->sw_storage_off, A->sw_storage_cnt,
+                          A->econ_life, A->loan_term, A->inflation, A->pv_deg, A->escalator, A->down_payment,
+                          A->tax_rate, A->real_discount, A->itc_frac, A->capex, A->capex_combined,
+                          A->batt_capex_kwh, A->ccm, A->vor};
+    for (const void* p : cols)
+        if (!p) { set_err("dgen_batt_curve_net: missing agent column"); return DGEN_E_ARG; }
+    if (!O->system_kw || !O->status || !O->tariff_final || !O->switched) {
+        set_err("dgen_batt_curve_net: missing output column (system_kw, tariff_final, switched, status of the "
+                "sizing call)");
+        return DGEN_E_ARG;
+    }
+    if (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1) {
+        set_err("dgen_batt_curve_net: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not replayed: the daily plan under constant efficiencies only");
+        return DGEN_E_ARG;
+    }
+    int cap = (opt && opt->cap > 0) ? opt->cap : DGEN_NB_CAPM;
+    if (cap > DGEN_NB_CAPM) {
+        set_err("dgen_batt_curve_net: cap = %d mixed hours per month, at most %d", cap, DGEN_NB_CAPM);
+        return DGEN_E_ARG;
+    }
+    const int64_t tiles = (n * K + BC_BLOCK - 1) / BC_BLOCK;
+    if (tiles > 0x7fffffff) {
+        set_err("dgen_batt_curve_net: K x n = %lld exceeds the launch grid", (long long)(n * K));
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    const size_t lds = (size_t)BN_PLANES * lds_half(T->max_periods) * BC_BLOCK * sizeof(double);
+    HIP_TRY(hipSetDevice(c->device));
+    if (lds > (size_t)c->lds_max) {
+        set_err("dgen_batt_curve_net: %zu B of LDS for %d periods exceed the device's %d B per block", lds,
+                lds_half(T->max_periods), c->lds_max);
+        return DGEN_E_ARG;
+    }
+    // persistent blocks: as many as the device holds at once (two waves per SIMD at most), each with its
+    // own workspace slice, striding over the 64-point tiles
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_batt_curve_net),
+                                                     BC_BLOCK, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
+    const int64_t resident = (int64_t)per_cu * c->n_cu;
+    const int64_t blocks = tiles < resident ? tiles : resident;
+    const size_t need = (size_t)blocks * bn_block_bytes(cap);
+    if (need > c->bn_ws_cap) {
+        if (c->bn_ws) HIP_TRY(hipFree(c->bn_ws));       // waits for the kernels that read it
+        c->bn_ws = nullptr;
+        c->bn_ws_cap = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&c->bn_ws), need) != hipSuccess) {
+            (void)hipGetLastError();
+            c->bn_ws = nullptr;
+            set_err("dgen_batt_curve_net: %zu B of workspace for %lld blocks of %d mixed hours", need,
+                    (long long)blocks, cap);
+            return DGEN_E_HIP;
+        }
+        c->bn_ws_cap = need;
+    }
+    hipLaunchKernelGGL(k_batt_curve_net, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A,
+                       *O, c->cfg, n, (int)K, c->battery, kwh, kw_pts, *out, c->bn_ws, cap);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

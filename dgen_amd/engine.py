@@ -761,7 +761,8 @@ class Engine:
         self._keep["_bill_kw"] = (k, t)       # alive until the next call (stream order)
         return res
 
-    def batt_curve(self, batch: AgentBatch, outputs, kwh, kw=None, want=None) -> Dict[str, object]:
+    def batt_curve(self, batch: AgentBatch, outputs, kwh, kw=None, want=None, net=False,
+                   net_cap=None) -> Dict[str, object]:
         """With-battery economics of `batch`, already sized or evaluated into
         `outputs` (the alloc_outputs dict, or its c_outputs; system_kw,
         tariff_final, switched and status are read, nothing is written), at K
@@ -774,8 +775,12 @@ class Engine:
         _lib.BATT_CURVE_FIELDS).  Returns {member: [K, n] device tensor}: npv,
         payback_raw, total_cost, bank_kwh, power_kw, bill_w_year1,
         bill_wo_year1, lifetime_savings (float64), tariff, switched, status
-        (int32; a point with a fatal status holds NaN).  The definitions are in
-        include/dgen_hip.h."""
+        (int32; a point with a fatal status holds NaN).  net=True follows with
+        dgen_batt_curve_net on the same buffers and stream: the points whose
+        tariff bills hourly imports (metering options 2 and 3) are computed
+        instead of flagged _lib.ST_HOURLY_FORM; net_cap: the mixed hours a
+        month may hold per point (default _lib.NB_CAPM; a point beyond it stays
+        flagged).  The definitions are in include/dgen_hip.h."""
         torch = _torch()
         want = tuple(_lib.BATT_CURVE_FIELDS if want is None else want)
         bad = [k for k in want if k not in _lib.BATT_CURVE_FIELDS]
@@ -805,6 +810,12 @@ class Engine:
         _lib.check(self.lib.dgen_batt_curve(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
                                             ctypes.byref(co), n, K, _ptr(e), _ptr(p), ctypes.byref(bo),
                                             self.stream_handle()), "dgen_batt_curve")
+        if net:
+            no = _lib.BattNetOpt(0 if net_cap is None else int(net_cap), 0)
+            _lib.check(self.lib.dgen_batt_curve_net(self.ctx, ctypes.byref(self.tables),
+                                                    ctypes.byref(batch.c_agents), ctypes.byref(co), n, K, _ptr(e),
+                                                    _ptr(p), ctypes.byref(no), ctypes.byref(bo),
+                                                    self.stream_handle()), "dgen_batt_curve_net")
         self._keep["_batt_curve"] = (e, p)    # alive until the next call (stream order)
         return res
 

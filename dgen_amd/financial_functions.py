@@ -633,8 +633,11 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     per agent the valid point of largest NPV: batt_opt_kwh, batt_opt_kw (the
     installed bank), batt_opt_npv, batt_opt_payback, batt_opt_point (-1: none),
     batt_opt_npv_gain (over the reference's point) and batt_opt_status.  No
-    plane is read: the same bits in every hourly mode and sub-batching.  None
-    (the default) leaves the frame unchanged."""
+    plane is read: the same bits in every hourly mode and sub-batching.  The
+    dict form's key "net_billing": True also computes the agents whose tariff
+    bills hourly imports (metering options 2 and 3: every CA agent and the
+    net-billing tariffs; dgen_batt_curve_net), which otherwise carry
+    batt_opt_point = -1.  None (the default) leaves the frame unchanged."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")

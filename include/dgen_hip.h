@@ -1023,6 +1023,60 @@ int32_t dgen_batt_curve(dgen_ctx* ctx, const dgen_tables* tables, const dgen_age
                         const dgen_outputs* sized, int64_t n, int32_t K, const double* kwh,
                         const double* kw_pts, const dgen_batt_curve_out* out, void* stream);
 
+/* Battery size what-if under net billing (additive to ABI 14): the points
+ * dgen_batt_curve leaves flagged DGEN_ST_HOURLY_FORM because their tariff
+ * bills hourly imports -- metering options 2 and 3, with the period sell rate
+ * or the hourly TS sell rate.  Arguments, layouts, the K range, the output
+ * struct and every DGEN_E_ARG case are dgen_batt_curve's.  The entry fills in:
+ * called after dgen_batt_curve on the same buffers and stream it overwrites
+ * exactly the points it covers and writes nothing else, so what stays flagged
+ * DGEN_ST_HOURLY_FORM is kWh/kW tier units, billed demand charges and
+ * overflow (below).  A covered point: the agent is sized (no DGEN_ST_BOUNDS,
+ * _TARIFF, _YEARS, _UNIT), kwh and kw_pts are valid as in dgen_batt_curve, the
+ * tariff after the storage rate switch is in range and within
+ * tables->max_periods, its metering option is 2 or 3, its tier unit 0 or 2,
+ * and no demand charge is billed.  Every other point -- bins-form tariffs
+ * included -- is not written at all, members and status alike.
+ * Per covered point: bank, power, dispatch replay -> sys[h], storage switch
+ * (sticky on the tariff_final / switched handed in), cost and Cashloan (the
+ * forward-sum NPV) are dgen_batt_curve's.  The bills are orc_ur5's hourly
+ * form: for year y = 1 .. N with s_y, r_y the sequential products, per
+ * (month, period) in hour order
+ *     d = ld[h] - s_y x sys[h];  imp += d when d > 0, else exv += (-d) x ts[h]
+ * with ts[h] = 1 without the TS rate; the month's bill is
+ *     mo 2: (fixed + E(imp)) - cr          mo 3: fixed + max(E(imp) - cr - carry, 0),
+ *           carry = max(-(E(imp) - cr - carry), 0) to the next month (lost at year end)
+ * E = month_energy_charge (as under dgen_bill_months), cr = sum_p exv[p] x
+ * sell[p][0], or sum_p exv[p] under the TS rate; bill_w[y] = r_y x the twelve
+ * months' sum; the no-system year bills imp = lbin with cr = 0.  The TS rate
+ * applies exactly as in dgen_bill_months: mo 2, not CA, wholesale_row >= 0,
+ * tables->wholesale non-NULL, ts[h] = (double)(float)(wholesale[h] x
+ * price_mult).
+ * The kernel re-associates the hourly sums as the scan's battery-case split
+ * does: over the agent's degradation range [s_N, 1] an hour importing at both
+ * ends (above -1e-10 x (|ld| + |sys| x s_hi): a near-zero battery hour counts
+ * as an import) adds ld and sys to two sums per (month, period), an hour
+ * exporting at both ends adds sys x ts and ld x ts to two more, and any other
+ * hour joins the month's mixed list, evaluated per year in hour order.  Results
+ * equal the hourly order to rounding, not bit for bit.
+ * opt->cap: the mixed hours a month's list holds per point, 1 ..
+ * DGEN_NB_CAPM (NULL or cap <= 0: DGEN_NB_CAPM; above it: DGEN_E_ARG).  A point
+ * with a month beyond cap is not written (overflow): it keeps what the buffers
+ * held, DGEN_ST_HOURLY_FORM after dgen_batt_curve.  Nothing is stored past cap.
+ * The lists live in a ctx-owned workspace sized by the blocks resident on the
+ * device (a persistent, grid-stride launch), not by K x n: per block 51,200 B
+ * of per-year accumulators and cap x 1024 B of entries, grown on demand and
+ * freed by dgen_close; calls on one ctx must be stream-ordered.  Points are
+ * independent (column k of a K-point call is the K = 1 call bit for bit), no
+ * atomics and no cross-lane sums: run-to-run identical.  The kernel keeps 7 x
+ * max_periods x 512 B of LDS per 64 points.                                   */
+typedef struct { int32_t cap; int32_t pad; } dgen_batt_net_opt;   /* NULL or cap <= 0: DGEN_NB_CAPM */
+
+int32_t dgen_batt_curve_net(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                            const dgen_outputs* sized, int64_t n, int32_t K, const double* kwh,
+                            const double* kw_pts, const dgen_batt_net_opt* opt,
+                            const dgen_batt_curve_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

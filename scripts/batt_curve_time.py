@@ -6,7 +6,13 @@ profile order) sized once, then 3 warm-ups + 20 timed runs each of
   dgen_batt_curve, K = 1       at the reference's point (kW* / 0.8, 2 h)
   dgen_batt_curve, K = 6       0, 0.25, 0.5, 1, 2, 4 x kW* / 0.8
 Prints one JSON line: the median times (ms), the K = 1 / summary ratio and the
-K = 6 time per point over the K = 1 time."""
+K = 6 time per point over the K = 1 time.
+
+--net: dgen_batt_curve_net alone (on buffers dgen_batt_curve filled) at K = 1
+and K = 6, beside dgen_batt_curve at K = 1 and the sizing call's own
+battery-case kernels (k_hourly_batt + k_batt_finance, dgen_kernel_times), which
+do the same work for the reference's point; the default population is then
+bench.py's ca_res_storage with 200 k agents in device order."""
 import argparse
 import json
 import os
@@ -17,11 +23,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--agents", type=int, default=1_000_000)
-    ap.add_argument("--config", default="res_1m_nem_tou")
+    ap.add_argument("--agents", type=int, default=None)
+    ap.add_argument("--config", default=None)
+    ap.add_argument("--net", action="store_true", help="time dgen_batt_curve_net (net-billing tariffs)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
     args = ap.parse_args()
+    if args.config is None:
+        args.config = "ca_res_storage" if args.net else "res_1m_nem_tou"
+    if args.agents is None:
+        args.agents = 200_000 if args.net else 1_000_000
     import numpy as np
     import torch
     from dgen_amd.config import EngineConfig
@@ -37,6 +48,12 @@ def main():
     out = eng.alloc_outputs(batch.n, hourly=False)
     eng.size(batch, out)
     torch.cuda.synchronize()
+    if args.net:
+        eng.kernel_times()                   # reset: the sizing call's kernels over the runs below alone
+        for _ in range(3):
+            eng.size(batch, out)
+        torch.cuda.synchronize()
+        k_size, k_hourly, k_finance, _ = eng.kernel_times()
     e = out["system_kw"] / 0.8
     one = e.view(1, -1).contiguous()
     six = torch.stack([f * e for f in (0.0, 0.25, 0.5, 1.0, 2.0, 4.0)]).contiguous()
@@ -56,6 +73,37 @@ def main():
         return float(np.median(ms)), float(min(ms)), float(max(ms))
 
     want = ("npv", "payback_raw", "bank_kwh", "power_kw", "status")
+    if args.net:
+        import ctypes
+        from dgen_amd import _lib
+        co = eng.c_outputs(out)
+
+        def net_call(pts):
+            res = eng.batt_curve(batch, out, pts, want=want)
+            bo = _lib.BattCurveOut(**{k: v.data_ptr() for k, v in res.items()})
+            no = _lib.BattNetOpt(0, 0)
+
+            def fn():
+                _lib.check(eng.lib.dgen_batt_curve_net(eng.ctx, ctypes.byref(eng.tables), ctypes.byref(batch.c_agents),
+                                                       ctypes.byref(co), batch.n, int(pts.shape[0]), pts.data_ptr(), None,
+                                                       ctypes.byref(no), ctypes.byref(bo), eng.stream_handle()),
+                           "dgen_batt_curve_net")
+            return fn, res
+        f1, r1 = net_call(one)
+        f6, r6 = net_call(six)
+        n1, n6 = timed(f1), timed(f6)
+        c1 = timed(lambda: eng.batt_curve(batch, out, one, want=want))
+        torch.cuda.synchronize()
+        print(json.dumps({"agents": batch.n, "config": args.config, "max_periods": int(pop.tariffs["P"].max()),
+                          "batt_curve_net_k1_ms": n1[0], "batt_curve_net_k6_ms": n6[0], "batt_curve_k1_ms": c1[0],
+                          "sizing_k_hourly_batt_ms": k_hourly, "sizing_k_batt_finance_ms": k_finance,
+                          "ratio_net_k1_over_sizing_battery_case": n1[0] / (k_hourly + k_finance),
+                          "k6_per_point_over_k1": n6[0] / 6.0 / n1[0],
+                          "min_max_ms": {"net_k1": n1[1:], "net_k6": n6[1:], "k1": c1[1:]},
+                          "points_flagged_k1": int((r1["status"] != 0).sum().item()),
+                          "points_flagged_k6": int((r6["status"] != 0).sum().item())}))
+        eng.close()
+        return
     s = timed(lambda: eng.batt_summary(batch, out))
     c1 = timed(lambda: eng.batt_curve(batch, out, one, want=want))
     c6 = timed(lambda: eng.batt_curve(batch, out, six, want=want))
