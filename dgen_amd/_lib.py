@@ -175,6 +175,17 @@ class BattNetOpt(ctypes.Structure):
     _fields_ = [("cap", _i32), ("pad", _i32)]
 
 
+BATT_PEAK_CAPM_MAX = NB_CAPM   # dgen_batt_peak_opt.cap_mixed: default and maximum (dgen_batt_curve_net's cap)
+BATT_PEAK_CAPK = 744           # include/dgen_hip.h DGEN_BATT_PEAK_CAPK (default kept hours per month and point)
+BATT_PEAK_CAPK_MAX = 744       # include/dgen_hip.h DGEN_BATT_PEAK_CAPK_MAX
+
+
+class BattPeakOpt(ctypes.Structure):
+    """dgen_batt_peak_opt: cap_mixed = dgen_batt_curve_net's cap, cap_kept = the kept hours a month's
+    demand record holds per point (<= 0: the defaults)."""
+    _fields_ = [("cap_mixed", _i32), ("cap_kept", _i32)]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -193,7 +204,7 @@ EXPORTED = [
     "dgen_set_pipeline", "dgen_set_hourly_segment", "dgen_set_battery", "dgen_set_nb_scan", "dgen_set_ts_rows", "dgen_set_nem_rows", "dgen_set_dc_records", "dgen_set_exact", "dgen_exact_count", "dgen_hourly_planes", "dgen_export_plane", "dgen_state_hourly_rows", "dgen_batt_attach", "dgen_export_weights", "dgen_state_hourly",
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
-    "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net",
+    "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
 ]
 
 
@@ -292,6 +303,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_batt_curve_net.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
                                       _i64, _i32, _vp, _vp, ctypes.POINTER(BattNetOpt),
                                       ctypes.POINTER(BattCurveOut), _vp]
+    L.dgen_batt_curve_peak.restype = _i32
+    L.dgen_batt_curve_peak.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
+                                       _i64, _i32, _vp, _vp, ctypes.POINTER(BattPeakOpt),
+                                       ctypes.POINTER(BattCurveOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

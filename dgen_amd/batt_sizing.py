@@ -18,8 +18,11 @@ options 0, 1, 4; tier units 0, 2; no billed demand charge); a point under
 another form carries _lib.ST_HOURLY_FORM and NaN, and is never a best point.
 net=True (the spec key "net_billing": True) adds dgen_batt_curve_net on the
 same buffers: the net-billing tariffs (options 2 and 3, the TS sell rate
-included) are computed too, and what stays flagged is kWh/kW tier units and
-billed demand charges.
+included) are computed too.  peak=True (the spec key "peak_billing": True)
+adds dgen_batt_curve_peak: tariffs with billed demand charges or kWh/kW tier
+units, under every metering option.  After all three what stays flagged is
+the agents the sizing call left DGEN_ST_UNIT, malformed demand tables and
+list overflow.
 """
 from __future__ import annotations
 
@@ -80,11 +83,13 @@ def _inverse(engine, perm):
 
 
 def curve_outputs(engine, batch, out, kwh, kw=None, want: Optional[Sequence[str]] = None,
-                  net: bool = False, net_cap: Optional[int] = None) -> Dict[str, object]:
+                  net: bool = False, net_cap: Optional[int] = None, peak: bool = False,
+                  peak_caps=None) -> Dict[str, object]:
     """Engine.batt_curve of a batch sized (or evaluated) into `out`, with kwh /
     kw given and the members returned in caller order (batch.perm):
-    {member: [K, n] device tensor}.  net / net_cap: Engine.batt_curve's (the
-    net-billing points computed too)."""
+    {member: [K, n] device tensor}.  net / net_cap and peak / peak_caps:
+    Engine.batt_curve's (the net-billing points, and the demand-charge and
+    kWh/kW-tier points, computed too)."""
     import torch
     e = engine._to_dev(kwh, torch.float64)
     p = None if kw is None else engine._to_dev(kw, torch.float64)
@@ -92,7 +97,7 @@ def curve_outputs(engine, batch, out, kwh, kw=None, want: Optional[Sequence[str]
         pm = engine._to_dev(np.asarray(batch.perm, np.int64), torch.int64)
         e = e.index_select(e.dim() - 1, pm)
         p = None if p is None else p.index_select(p.dim() - 1, pm)
-    d = engine.batt_curve(batch, out, e, p, want, **_net_kw(net, net_cap))
+    d = engine.batt_curve(batch, out, e, p, want, **_net_kw(net, net_cap), **_peak_kw(peak, peak_caps))
     inv = _inverse(engine, batch.perm)
     if inv is None:
         return d
@@ -105,6 +110,13 @@ def _net_kw(net, net_cap=None):
     if not net:
         return {}
     return {"net": True} if net_cap is None else {"net": True, "net_cap": net_cap}
+
+
+def _peak_kw(peak, peak_caps=None):
+    """Engine.batt_curve's keywords; none without peak, as _net_kw."""
+    if not peak:
+        return {}
+    return {"peak": True} if peak_caps is None else {"peak": True, "peak_caps": peak_caps}
 
 
 def best_point(curve: Dict[str, object]):
@@ -167,11 +179,12 @@ def summarize(curve: Dict[str, object], ref_point: int) -> Dict[str, object]:
 def grid(spec) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
     """size_frame's batt_sizing spec as (pv_to_batt, hours): a dict with either
     key, a (pv_to_batt, hours) pair, or True for the default grid.  The dict's
-    "net_billing" key is not part of the grid (net_billing(spec))."""
+    "net_billing" and "peak_billing" keys are not part of the grid
+    (net_billing(spec), peak_billing(spec))."""
     if spec is True:
         return (0.4, 0.8, 1.6), (1.0, 2.0, 4.0)
     if isinstance(spec, dict):
-        bad = set(spec) - {"pv_to_batt", "hours", "net_billing"}
+        bad = set(spec) - {"pv_to_batt", "hours", "net_billing", "peak_billing"}
         if bad:
             raise ValueError(f"batt_sizing: unknown keys {sorted(bad)}")
         return tuple(spec.get("pv_to_batt", (REF_PV_TO_BATT,))), tuple(spec.get("hours", (REF_HOURS,)))
@@ -185,6 +198,12 @@ def net_billing(spec) -> bool:
     return isinstance(spec, dict) and bool(spec.get("net_billing", False))
 
 
+def peak_billing(spec) -> bool:
+    """True when the spec asks for the demand-charge and kWh/kW-tier tariffs
+    too: a dict with "peak_billing": True."""
+    return isinstance(spec, dict) and bool(spec.get("peak_billing", False))
+
+
 def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     """The drop-in switch's per-agent columns (COLUMNS) of a sized output dict
     as host arrays in caller order: the curve over ratio_points(system_kw,
@@ -192,7 +211,8 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     point, reduced by summarize().  float64, except batt_opt_point and
     batt_opt_status (int64).  Only these [n] vectors cross to the host.  With
     "net_billing": True in the spec the net-billing points are computed too
-    (dgen_batt_curve_net)."""
+    (dgen_batt_curve_net), with "peak_billing": True the points on tariffs
+    with billed demand charges or kWh/kW tier units (dgen_batt_curve_peak)."""
     import torch
     r, h = grid(spec)
     skw = out["system_kw"]
@@ -204,7 +224,7 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
                          f"{_lib.BATT_CURVE_MAX_POINTS}")
     # an unsized agent's system_kw may be NaN: its points are flagged, not read
     d = engine.batt_curve(batch, out, kwh, kw, ("npv", "payback_raw", "bank_kwh", "power_kw", "status"),
-                          **_net_kw(net_billing(spec)))
+                          **_net_kw(net_billing(spec)), **_peak_kw(peak_billing(spec)))
     s = summarize(d, int(kwh.shape[0]) - 1)
     inv = _inverse(engine, batch.perm)
     res = {}

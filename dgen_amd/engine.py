@@ -762,7 +762,7 @@ class Engine:
         return res
 
     def batt_curve(self, batch: AgentBatch, outputs, kwh, kw=None, want=None, net=False,
-                   net_cap=None) -> Dict[str, object]:
+                   net_cap=None, peak=False, peak_caps=None) -> Dict[str, object]:
         """With-battery economics of `batch`, already sized or evaluated into
         `outputs` (the alloc_outputs dict, or its c_outputs; system_kw,
         tariff_final, switched and status are read, nothing is written), at K
@@ -780,7 +780,14 @@ class Engine:
         tariff bills hourly imports (metering options 2 and 3) are computed
         instead of flagged _lib.ST_HOURLY_FORM; net_cap: the mixed hours a
         month may hold per point (default _lib.NB_CAPM; a point beyond it stays
-        flagged).  The definitions are in include/dgen_hip.h."""
+        flagged).  peak=True follows with dgen_batt_curve_peak, again on the
+        same buffers and stream: the points whose tariff bills demand charges
+        or has kWh/kW tier units are computed, under every metering option;
+        it implies nothing about net (pass both for full coverage).
+        peak_caps: (cap_mixed, cap_kept), the mixed hours and the kept hours of
+        the demand record a month may hold per point (defaults _lib.NB_CAPM and
+        _lib.BATT_PEAK_CAPK; None or 0 for either: its default; a point beyond
+        either stays flagged).  The definitions are in include/dgen_hip.h."""
         torch = _torch()
         want = tuple(_lib.BATT_CURVE_FIELDS if want is None else want)
         bad = [k for k in want if k not in _lib.BATT_CURVE_FIELDS]
@@ -816,6 +823,13 @@ class Engine:
                                                     ctypes.byref(batch.c_agents), ctypes.byref(co), n, K, _ptr(e),
                                                     _ptr(p), ctypes.byref(no), ctypes.byref(bo),
                                                     self.stream_handle()), "dgen_batt_curve_net")
+        if peak:
+            cm, ck = (0, 0) if peak_caps is None else peak_caps
+            po = _lib.BattPeakOpt(int(cm or 0), int(ck or 0))
+            _lib.check(self.lib.dgen_batt_curve_peak(self.ctx, ctypes.byref(self.tables),
+                                                     ctypes.byref(batch.c_agents), ctypes.byref(co), n, K, _ptr(e),
+                                                     _ptr(p), ctypes.byref(po), ctypes.byref(bo),
+                                                     self.stream_handle()), "dgen_batt_curve_peak")
         self._keep["_batt_curve"] = (e, p)    # alive until the next call (stream order)
         return res
 

@@ -637,7 +637,9 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     dict form's key "net_billing": True also computes the agents whose tariff
     bills hourly imports (metering options 2 and 3: every CA agent and the
     net-billing tariffs; dgen_batt_curve_net), which otherwise carry
-    batt_opt_point = -1.  None (the default) leaves the frame unchanged."""
+    batt_opt_point = -1; its key "peak_billing": True those whose tariff bills
+    demand charges or has kWh/kW tier units (dgen_batt_curve_peak).  None (the
+    default) leaves the frame unchanged."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")

@@ -1077,6 +1077,77 @@ int32_t dgen_batt_curve_net(dgen_ctx* ctx, const dgen_tables* tables, const dgen
                             const double* kw_pts, const dgen_batt_net_opt* opt,
                             const dgen_batt_curve_out* out, void* stream);
 
+/* Battery size what-if with month peaks (additive to ABI 14): the points the
+ * two entries above leave flagged DGEN_ST_HOURLY_FORM because their tariff
+ * bills demand charges or has kWh/kW tier units (codes 1, 3), under every
+ * metering option.  Arguments, layouts, the K range, the output struct and
+ * every DGEN_E_ARG case are dgen_batt_curve_net's.  The entry fills in: called
+ * after dgen_batt_curve (and dgen_batt_curve_net, in either order) on the same
+ * buffers and stream it overwrites exactly the points it covers and writes
+ * nothing else, members and status alike.  A covered point: the agent is sized
+ * (no DGEN_ST_BOUNDS, _TARIFF, _YEARS, _UNIT), kwh and kw_pts are valid as in
+ * dgen_batt_curve, the tariff after the storage rate switch is in range and
+ * within tables->max_periods, and that tariff has tier unit 1 or 3 or demand
+ * charges are billed for it (cfg.skip_demand_charges == 0 and tariff.dc names
+ * a record in 1 .. n_demand).  Not written, so still flagged: a point whose
+ * tariff or demand record carries DGEN_ST_DEMAND, one whose demand schedule
+ * names a period at or beyond tables->max_dc_periods, and overflow (below).
+ * After the three calls DGEN_ST_HOURLY_FORM means a DGEN_ST_UNIT agent, a
+ * malformed demand table or list overflow.
+ * Per covered point: bank, power, dispatch replay -> sys[h], storage switch
+ * (sticky on the tariff_final / switched handed in), cost and Cashloan (the
+ * forward-sum NPV) are dgen_batt_curve's.  The bills are orc_ur5's with peaks:
+ * for year y = 1 .. N with s_y, r_y the sequential products, month m, demand
+ * period q (the record's schedule; one period when a kWh/kW tariff has no
+ * record)
+ *     peak_y[m][q] = max(0, max over the hours of (m, q) of ld[h] - s_y x sys[h])
+ *     flat_y[m]    = max_q peak_y[m][q]
+ * E(u, peak) = month_energy_charge with the tier caps x flat_y[m] (unit 1) or
+ * x flat_y[m] x days (unit 3).  The month's energy side is dgen_batt_curve's
+ * for metering options 0, 1 and 4 (from the month's bins at lbin - s_y x gbin)
+ * and dgen_batt_curve_net's for options 2 and 3 (hourly imports and exports,
+ * the TS rate as there, re-associated by its linear-sums / mixed-list rule
+ * with the same 1e-10 slack: equal to the hourly order to rounding).  The
+ * month's demand charge, when billed, is dc_tier_charge(flat_y[m], the
+ * month's flat tiers), then + dc_tier_charge(peak_y[m][q], period q's tiers)
+ * for q ascending.  Each year keeps two running sums in month order and adds
+ * them once: bill_w[y] = r_y x (sum_m energy bill + sum_m demand charge); the
+ * no-system year bills ld alone, its peaks the (m, q) maxima of the load.
+ * The peaks come from a per-point demand record, built per month by the
+ * scan's rule over [s_lo, s_hi] = [s_N, 1]: per (m, q) the running
+ * lb = max_h min(d(s_lo), d(s_hi)) and, in hour order, the hours whose
+ * max(d(s_lo), d(s_hi)) exceeds lb as it stood before them, compacted at the
+ * month's end against the final lb.  fl(ld - fl(sys x s)) is monotone in s, so
+ * a dropped hour is at or below an earlier hour in every year and lb is at or
+ * below every year's peak: each year's peak over the kept hours, started from
+ * lb, is its peak over all hours bit for bit.
+ * opt->cap_mixed: dgen_batt_curve_net's cap (default and maximum
+ * DGEN_NB_CAPM); opt->cap_kept: the kept hours a month's list holds per point
+ * before compaction, 1 .. DGEN_BATT_PEAK_CAPK_MAX (a month's 744 hours: no
+ * overflow), default DGEN_BATT_PEAK_CAPK, the maximum as well: a bank that
+ * covers the whole load leaves lb at 0 and keeps nearly every hour (DESIGN.md
+ * section 5).  NULL or a value <= 0: the default; above the maximum:
+ * DGEN_E_ARG.  A point with a month beyond either cap is
+ * not written; nothing is stored past a cap.  The lists and the per-year state
+ * (energy total, demand total, dollar carry, and the kWh credit bank per
+ * period of option 0, for the no-system year and N years) live in a ctx-owned
+ * workspace sized by the blocks resident on the device (a persistent,
+ * grid-stride launch), not by K x n: per block 26,112 x (3 + max_periods) B
+ * of per-year state and (cap_mixed + cap_kept) x 1024 B of entries, grown on
+ * demand and freed by dgen_close; calls on one ctx must be stream-ordered.
+ * Points are independent (column k of a K-point call is the K = 1 call bit
+ * for bit), no atomics and no cross-lane sums: run-to-run identical.  The
+ * kernel keeps (7 x max_periods + 3 x max_dc_periods) x 512 B of LDS per 64
+ * points.                                                                     */
+#define DGEN_BATT_PEAK_CAPK      744   /* default kept hours per month and point */
+#define DGEN_BATT_PEAK_CAPK_MAX  744   /* a month's hours                        */
+typedef struct { int32_t cap_mixed; int32_t cap_kept; } dgen_batt_peak_opt;   /* NULL or <= 0: the defaults */
+
+int32_t dgen_batt_curve_peak(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                             const dgen_outputs* sized, int64_t n, int32_t K, const double* kwh,
+                             const double* kw_pts, const dgen_batt_peak_opt* opt,
+                             const dgen_batt_curve_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,10 @@ K = 6 time per point over the K = 1 time.
 and K = 6, beside dgen_batt_curve at K = 1 and the sizing call's own
 battery-case kernels (k_hourly_batt + k_batt_finance, dgen_kernel_times), which
 do the same work for the reference's point; the default population is then
-bench.py's ca_res_storage with 200 k agents in device order."""
+bench.py's ca_res_storage with 200 k agents in device order.
+
+--peak: the same for dgen_batt_curve_peak (demand charges, kWh/kW tiers); the
+default population is bench.py's com_dc_batt with 200 k agents."""
 import argparse
 import json
 import os
@@ -26,13 +29,15 @@ def main():
     ap.add_argument("--agents", type=int, default=None)
     ap.add_argument("--config", default=None)
     ap.add_argument("--net", action="store_true", help="time dgen_batt_curve_net (net-billing tariffs)")
+    ap.add_argument("--peak", action="store_true", help="time dgen_batt_curve_peak (demand charges, kWh/kW tiers)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
     args = ap.parse_args()
+    fill = args.net or args.peak
     if args.config is None:
-        args.config = "ca_res_storage" if args.net else "res_1m_nem_tou"
+        args.config = "com_dc_batt" if args.peak else "ca_res_storage" if args.net else "res_1m_nem_tou"
     if args.agents is None:
-        args.agents = 200_000 if args.net else 1_000_000
+        args.agents = 200_000 if fill else 1_000_000
     import numpy as np
     import torch
     from dgen_amd.config import EngineConfig
@@ -48,7 +53,7 @@ def main():
     out = eng.alloc_outputs(batch.n, hourly=False)
     eng.size(batch, out)
     torch.cuda.synchronize()
-    if args.net:
+    if fill:
         eng.kernel_times()                   # reset: the sizing call's kernels over the runs below alone
         for _ in range(3):
             eng.size(batch, out)
@@ -73,33 +78,36 @@ def main():
         return float(np.median(ms)), float(min(ms)), float(max(ms))
 
     want = ("npv", "payback_raw", "bank_kwh", "power_kw", "status")
-    if args.net:
+    if fill:
         import ctypes
         from dgen_amd import _lib
         co = eng.c_outputs(out)
+        name = "dgen_batt_curve_peak" if args.peak else "dgen_batt_curve_net"
+        tag = "peak" if args.peak else "net"
 
         def net_call(pts):
             res = eng.batt_curve(batch, out, pts, want=want)
             bo = _lib.BattCurveOut(**{k: v.data_ptr() for k, v in res.items()})
-            no = _lib.BattNetOpt(0, 0)
+            no = _lib.BattPeakOpt(0, 0) if args.peak else _lib.BattNetOpt(0, 0)
+            entry = getattr(eng.lib, name)
 
             def fn():
-                _lib.check(eng.lib.dgen_batt_curve_net(eng.ctx, ctypes.byref(eng.tables), ctypes.byref(batch.c_agents),
-                                                       ctypes.byref(co), batch.n, int(pts.shape[0]), pts.data_ptr(), None,
-                                                       ctypes.byref(no), ctypes.byref(bo), eng.stream_handle()),
-                           "dgen_batt_curve_net")
+                _lib.check(entry(eng.ctx, ctypes.byref(eng.tables), ctypes.byref(batch.c_agents), ctypes.byref(co),
+                                 batch.n, int(pts.shape[0]), pts.data_ptr(), None, ctypes.byref(no), ctypes.byref(bo),
+                                 eng.stream_handle()), name)
             return fn, res
         f1, r1 = net_call(one)
         f6, r6 = net_call(six)
         n1, n6 = timed(f1), timed(f6)
+        torch.cuda.synchronize()             # the buffers now hold what the fill-in wrote
         c1 = timed(lambda: eng.batt_curve(batch, out, one, want=want))
         torch.cuda.synchronize()
         print(json.dumps({"agents": batch.n, "config": args.config, "max_periods": int(pop.tariffs["P"].max()),
-                          "batt_curve_net_k1_ms": n1[0], "batt_curve_net_k6_ms": n6[0], "batt_curve_k1_ms": c1[0],
+                          f"batt_curve_{tag}_k1_ms": n1[0], f"batt_curve_{tag}_k6_ms": n6[0], "batt_curve_k1_ms": c1[0],
                           "sizing_k_hourly_batt_ms": k_hourly, "sizing_k_batt_finance_ms": k_finance,
-                          "ratio_net_k1_over_sizing_battery_case": n1[0] / (k_hourly + k_finance),
+                          f"ratio_{tag}_k1_over_sizing_battery_case": n1[0] / (k_hourly + k_finance),
                           "k6_per_point_over_k1": n6[0] / 6.0 / n1[0],
-                          "min_max_ms": {"net_k1": n1[1:], "net_k6": n6[1:], "k1": c1[1:]},
+                          "min_max_ms": {f"{tag}_k1": n1[1:], f"{tag}_k6": n6[1:], "k1": c1[1:]},
                           "points_flagged_k1": int((r1["status"] != 0).sum().item()),
                           "points_flagged_k6": int((r6["status"] != 0).sum().item())}))
         eng.close()
