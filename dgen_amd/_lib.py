@@ -186,6 +186,24 @@ class BattPeakOpt(ctypes.Structure):
     _fields_ = [("cap_mixed", _i32), ("cap_kept", _i32)]
 
 
+SWB_F64 = ["system_kw", "npv", "payback_raw", "total_cost", "bank_kwh", "power_kw", "bill_w_year1",
+           "bill_wo_year1", "lifetime_savings"]
+SWB_I32 = ["nfev", "tariff", "switched", "status"]
+SWB_FIELDS = SWB_F64 + SWB_I32
+SWB_TRACE_MAX = 32   # include/dgen_hip.h DGEN_SWB_TRACE_MAX
+
+
+class SwbOpt(ctypes.Structure):
+    """dgen_swb_opt: desired_kwh = x / pv_to_batt_ratio, desired_kw = desired_kwh / hours (<= 0: 0.8, 2.0);
+    trace_n evaluations recorded per agent."""
+    _fields_ = [("pv_to_batt_ratio", _f64), ("hours", _f64), ("trace_n", _i32), ("pad", _i32)]
+
+
+class SwbOut(ctypes.Structure):
+    """dgen_swb_out: [n] device columns (any but status may be NULL) and the [n][trace_n] traces."""
+    _fields_ = [(name, _vp) for name in SWB_FIELDS] + [("trace_x", _vp), ("trace_f", _vp)]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -205,6 +223,7 @@ EXPORTED = [
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
     "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
+    "dgen_size_with_batt",
 ]
 
 
@@ -307,6 +326,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_batt_curve_peak.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
                                        _i64, _i32, _vp, _vp, ctypes.POINTER(BattPeakOpt),
                                        ctypes.POINTER(BattCurveOut), _vp]
+    L.dgen_size_with_batt.restype = _i32
+    L.dgen_size_with_batt.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _i64, _vp, _vp,
+                                      ctypes.POINTER(SwbOpt), ctypes.POINTER(SwbOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

@@ -23,6 +23,15 @@ adds dgen_batt_curve_peak: tariffs with billed demand charges or kWh/kW tier
 units, under every metering option.  After all three what stays flagged is
 the agents the sizing call left DGEN_ST_UNIT, malformed demand tables and
 list overflow.
+
+All of the above hold the PV size at kW*.  ``Engine.size_with_batt``
+(dgen_size_with_batt) instead searches the PV size x on the with-battery
+objective, the bank sized from x (x / ratio kWh at hours):
+
+    co_size_spec(spec)                           size_frame's pv_batt_sizing spec as (ratio, hours)
+    co_size_summarize(res, npv_ref, status_ref)  the CO_COLUMNS of a search result
+    co_size_columns(engine, batch, out, spec)    the per-agent columns of the drop-in switch
+                                                 (financial_functions.size_frame(pv_batt_sizing=spec))
 """
 from __future__ import annotations
 
@@ -39,6 +48,10 @@ COLUMNS = tuple(PREFIX + k for k in ("kwh", "kw", "npv", "payback", "point", "np
 # status bits that leave a point without a value
 INVALID = (_lib.ST_BOUNDS | _lib.ST_TARIFF | _lib.ST_YEARS | _lib.ST_SCRATCH | _lib.ST_UNIT | _lib.ST_DEMAND
            | _lib.ST_HOURLY_FORM)
+
+
+CO_PREFIX = "pvb_opt_"
+CO_COLUMNS = tuple(CO_PREFIX + k for k in ("kw", "kwh", "batt_kw", "npv", "payback", "nfev", "status", "npv_gain"))
 
 
 def _xp(t):
@@ -229,6 +242,69 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     inv = _inverse(engine, batch.perm)
     res = {}
     for k in COLUMNS:
+        t = s[k] if inv is None else s[k].index_select(0, inv)
+        if t.dtype == torch.int32:
+            t = t.to(torch.int64)
+        res[k] = t.cpu().numpy()
+    return res
+
+
+def co_size_spec(spec) -> Tuple[float, float]:
+    """size_frame's pv_batt_sizing spec as (ratio, hours): True for the
+    reference's constants (0.8, 2.0), or a dict with "ratio" and / or "hours";
+    both must be finite and positive."""
+    if spec is True:
+        return REF_PV_TO_BATT, REF_HOURS
+    if not isinstance(spec, dict):
+        raise ValueError(f"pv_batt_sizing: True or a dict with \"ratio\" / \"hours\" (got {spec!r})")
+    bad = set(spec) - {"ratio", "hours"}
+    if bad:
+        raise ValueError(f"pv_batt_sizing: unknown keys {sorted(bad)}")
+    r, h = float(spec.get("ratio", REF_PV_TO_BATT)), float(spec.get("hours", REF_HOURS))
+    if not (np.isfinite(r) and r > 0.0 and np.isfinite(h) and h > 0.0):
+        raise ValueError(f"pv_batt_sizing: ratio and hours must be finite and positive (got {r}, {h})")
+    return r, h
+
+
+def co_size_summarize(res: Dict[str, object], npv_ref, status_ref) -> Dict[str, object]:
+    """The CO_COLUMNS of an Engine.size_with_batt result ([n] each; numpy or
+    torch as the result is).  npv_ref, status_ref: npv_pv_batt and status of
+    the sizing call, in the same order.
+      pvb_opt_kw, _kwh, _batt_kw   system_kw and the installed bank and power at it
+      pvb_opt_npv, pvb_opt_payback npv and payback_raw at it
+      pvb_opt_nfev, pvb_opt_status the search's evaluations and status
+      pvb_opt_npv_gain             pvb_opt_npv - npv_ref; NaN where the search's
+                                   status has an INVALID bit or its npv is NaN,
+                                   or status_ref has an INVALID bit or npv_ref
+                                   is NaN
+    An agent whose search is invalid holds NaN in every float column (the
+    device wrote them)."""
+    xp = _xp(res["npv"])
+    npv = res["npv"]
+    ok = (((res["status"] & INVALID) == 0) & ~xp.isnan(npv)
+          & ((status_ref & INVALID) == 0) & ~xp.isnan(npv_ref))
+    gain = xp.where(ok, npv - npv_ref, xp.full_like(npv, np.nan))
+    return {CO_PREFIX + "kw": res["system_kw"], CO_PREFIX + "kwh": res["bank_kwh"],
+            CO_PREFIX + "batt_kw": res["power_kw"], CO_PREFIX + "npv": npv,
+            CO_PREFIX + "payback": res["payback_raw"], CO_PREFIX + "nfev": res["nfev"],
+            CO_PREFIX + "status": res["status"], CO_PREFIX + "npv_gain": gain}
+
+
+def co_size_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
+    """The drop-in switch's per-agent columns (CO_COLUMNS) as host arrays in
+    caller order: Engine.size_with_batt of the batch over the sizing call's
+    bracket at co_size_spec(spec), reduced by co_size_summarize() against the
+    npv_pv_batt and status of the sized output dict `out`.  float64, except
+    pvb_opt_nfev and pvb_opt_status (int64).  Only these [n] vectors cross to
+    the host."""
+    import torch
+    r, h = co_size_spec(spec)
+    d = engine.size_with_batt(batch, r, h, want=("system_kw", "bank_kwh", "power_kw", "npv", "payback_raw", "nfev",
+                                                 "status"))
+    s = co_size_summarize(d, out["npv_pv_batt"], out["status"])
+    inv = _inverse(engine, batch.perm)
+    res = {}
+    for k in CO_COLUMNS:
         t = s[k] if inv is None else s[k].index_select(0, inv)
         if t.dtype == torch.int32:
             t = t.to(torch.int64)

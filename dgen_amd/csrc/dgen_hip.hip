@@ -8426,6 +8426,306 @@ k_batt_curve_peak(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, in
     for (int64_t o = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; o < total; o += step)
         bp_point(T, A, O, cfg, n, o, batt_on, kwh_pts, kw_pts, S, lds, PH, dc_nq, accw, ent, capm, kept, capk);
 }
+
+// ---------------------------------------------------------------------------
+// PV sizing on the with-battery objective (dgen_size_with_batt; the definition
+// is in include/dgen_hip.h): scipy's bounded Brent (brent_bounded) over the PV
+// size x with the dgen_batt_curve point at (system_kw = x, kwh = x / ratio,
+// kw = kwh / hours), started from (tariff0, not switched), as its objective.
+// One lane per agent; k_batt_curve's LDS layout and year walk, run once per
+// evaluation.  Nothing in the objective is wave-collective, so the lanes of a
+// wave whose searches differ in length simply diverge.
+// swb_point is k_batt_curve's body, operation for operation (a copy: that
+// kernel's registers stay as they are); it reads the agent's columns again at
+// every evaluation, so that nothing but the search's own state lives across
+// the walk.  The bins forms of dgen_batt_curve_net and _peak would stand
+// beside it as further functions of (x, ratio, hours).
+// ---------------------------------------------------------------------------
+constexpr int SWB_FATAL = DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_YEARS | DGEN_ST_HOURLY_FORM;
+
+__device__ __forceinline__ void swb_store(const dgen_swb_out& S, int64_t i, const BcPoint& a) {
+    if (S.npv) S.npv[i] = a.npv;
+    if (S.payback_raw) S.payback_raw[i] = a.payback;
+    if (S.total_cost) S.total_cost[i] = a.cost;
+    if (S.bank_kwh) S.bank_kwh[i] = a.bank;
+    if (S.power_kw) S.power_kw[i] = a.power;
+    if (S.bill_w_year1) S.bill_w_year1[i] = a.w1;
+    if (S.bill_wo_year1) S.bill_wo_year1[i] = a.wo1;
+    if (S.lifetime_savings) S.lifetime_savings[i] = a.life;
+    if (S.tariff) S.tariff[i] = a.tariff;
+    if (S.switched) S.switched[i] = a.switched;
+    S.status[i] = a.status;
+}
+
+// The objective: -npv of the point, its members in `a`.  A point that cannot
+// be valued leaves NaN members, its status in a.status (a bit of SWB_FATAL)
+// and returns NaN.  The caller has checked tariff0 and the economic life.
+__device__ __forceinline__ double swb_point(const dgen_tables& T, const dgen_agents& A, const dgen_cfg& cfg, int64_t i,
+                                            int batt_on, double* lds, int PH, double x, double ratio, double hours,
+                                            BcPoint& a) {
+    const double q = __builtin_nan("");
+    int tariff = A.tariff0[i], switched = 0;
+    a = {q, q, q, q, q, q, q, q, tariff, switched, 0};
+    const double desired_kwh = x / ratio;
+    const double desired_kw = desired_kwh / hours;
+    int status = 0;
+    if (!(desired_kwh >= 0.0) || isinf(desired_kwh)) status |= DGEN_ST_BOUNDS;
+    else if (desired_kwh > 0.0 && (!(desired_kw > 0.0) || isinf(desired_kw))) status |= DGEN_ST_BOUNDS;
+    if (status) {
+        a.status = status;
+        return q;
+    }
+    int info = T.tariffs[tariff].flags;
+    const int N = A.econ_life[i];
+    const bool is_res = (A.flags[i] & 1) != 0;
+    const double kw_star = x;
+    double bank = 0.0, power = 0.0;
+    if (batt_on) batt_size(desired_kw, desired_kwh, is_res ? 240.0 : 500.0, cfg, &bank, &power);
+    double otc = 0.0;
+    if (bank > 0.0) {       // the storage rate switch on the point's bank, from (tariff0, not switched)
+        int nt = -1;
+        otc = rate_switch(T.switches + A.sw_storage_off[i], A.sw_storage_cnt[i], bank, &nt);
+        if (nt != -1) {
+            tariff = nt;
+            switched = 1;
+        }
+    }
+    a.tariff = tariff;
+    a.switched = switched;
+    if (tariff < 0 || tariff >= T.n_tariffs) {
+        a.status = DGEN_ST_TARIFF;
+        return q;
+    }
+    const dgen_tariff& t = T.tariffs[tariff];
+    const int P = t.P;
+    // a table whose max_periods does not cover the tariff is malformed
+    if (P < 1 || P > PH || t.T < 1 || t.T > MAXT) status |= DGEN_ST_TARIFF;
+    // hourly imports, billed demand charges, kWh/kW tiers: not this objective's forms
+    if (net_hourly(t) || peak_unit(t) || tariff_demand(T, cfg, t) != nullptr) status |= DGEN_ST_HOURLY_FORM;
+    if (status) {
+        a.status = status;
+        return q;
+    }
+    info |= t.flags;
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double ls = A.load_kwh[i] / T.shape_sum[lr];
+    const double cs6 = (((kw_star * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    const char* const esch = reinterpret_cast<const char*>(t.wkday);
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    double soc = cfg.batt_init_soc;
+    BcDay cur, nxt;
+    bc_day_load(shp, cfp, esch, 0, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        for (int p = 0; p < P; p++) {
+            lds[(m * PH + p) * BC_BLOCK] = 0.0;
+            lds[((12 + m) * PH + p) * BC_BLOCK] = 0.0;
+        }
+        int bcur = 0;
+        double b_ld = 0.0, b_gen = 0.0, mfloor = 0.0;
+        const int d_end = c_month_start_day[m + 1];
+        for (int d = c_month_start_day[m]; d < d_end; d++) {
+            {   // the next day's rows (December 31 loads itself again)
+                const int dn = d < 364 ? d + 1 : 364;
+                bc_day_load(shp, cfp, esch, dn, dn < d_end ? m : m + 1, nxt);
+            }
+            double dv[24];
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++)
+                dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+            sort24_desc(dv);
+            const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+            double target = day_target_sorted(dv, power, avail0);
+            {   // dgen_cfg.batt_month_floor: the month's target never falls
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                const double ld = (double)opaque_f(cur.s[hh >> 2][hh & 3]) * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                const HourStep hs = batt_hour(ld - pv, pv, target, power, bank, soc, cfg, inv_eta_in, in_per_bank,
+                                              out_per_bank);
+                int p = (int)((cur.e[hh >> 3] >> (8 * (hh & 7))) & 0xffu);
+                p = p < P ? p : P - 1;                  // a schedule beyond P: never past the lane's bins
+                if (p != bcur) {
+                    lds[(m * PH + bcur) * BC_BLOCK] = b_ld;
+                    lds[((12 + m) * PH + bcur) * BC_BLOCK] = b_gen;
+                    bcur = p;
+                    b_ld = lds[(m * PH + p) * BC_BLOCK];
+                    b_gen = lds[((12 + m) * PH + p) * BC_BLOCK];
+                }
+                b_ld += ld;
+                b_gen += hs.sys;
+            }
+            cur = nxt;
+        }
+        lds[(m * PH + bcur) * BC_BLOCK] = b_ld;
+        lds[((12 + m) * PH + bcur) * BC_BLOCK] = b_gen;
+    }
+    // ---- the N years' bills (oracle orc_ur5) and the Cashloan (orc_cashloan), year by year ----
+    const double rate_base = 1.0 + (A.inflation[i] * 100.0) * 0.01 + (A.escalator[i] * 100.0) * 0.01;
+    const double sys_base = 1.0 - (A.pv_deg[i] * 100.0) * 0.01;
+    const double vor = A.vor[i];
+    const double system_costs = (kw_star > 0.0) ? A.capex_combined[i] * kw_star : A.capex[i] * kw_star;
+    const double batt_costs = A.batt_capex_kwh[i] * bank * 0.7;
+    const double C = ((system_costs + batt_costs) * A.ccm[i]) + 0.0 + otc;
+    const int market = is_res ? 0 : 1, depr_type = is_res ? 0 : 2;
+    const double infl = (A.inflation[i] * 100.0) * 0.01;
+    const double real = (A.real_discount[i] * 100.0) * 0.01;
+    const double nom = (1.0 + real) * (1.0 + infl) - 1.0;
+    const double fed = ((A.tax_rate[i] * 100.0) * 0.7) * 0.01, sta = ((A.tax_rate[i] * 100.0) * 0.3) * 0.01;
+    const double debt = (100.0 - (A.down_payment[i] * 100.0)) * 0.01 * C;
+    const double r = cfg.loan_rate_pct * 0.01;
+    const int term = A.loan_term[i];
+    double pmt = 0.0;
+    if (term > 0 && debt != 0.0) {
+        if (r != 0.0) {
+            const double f = pow_seq(1.0 + r, term);
+            pmt = debt * r / (1.0 - 1.0 / f);
+        } else {
+            pmt = debt / (double)term;
+        }
+    }
+    double itc = A.itc_frac[i] * 0.01 * C;
+    if (itc > cfg.itc_fed_max) itc = cfg.itc_fed_max;
+    const double basis = C - 0.5 * itc;
+    const double ins = cfg.insurance_rate_pct * 0.01 * C;
+    const double rr = 1.0 / (1.0 + nom);
+    const double wo_base = bc_year_bill(t, lds, PH, 1.0, false, cfg.nm_yearend_sell_rate);
+    a.w1 = 0.0;
+    a.wo1 = 0.0;
+    a.life = 0.0;
+    double balance = debt, acc = 0.0, df = rr, cum = -C, pb = 1e99;
+    bool paid = false;
+    double r_y = 1.0, s_y = 1.0, o_y = 1.0;       // pow_seq's running products
+    for (int y = 1; y <= N; y++) {
+        const double w = bc_year_bill(t, lds, PH, s_y, true, cfg.nm_yearend_sell_rate) * r_y;
+        const double wo = wo_base * r_y;
+        const double ev = (wo - w) + vor;           // ff:275
+        if (y == 1) {
+            a.w1 = w;
+            a.wo1 = wo;
+        }
+        a.life += ev;
+        const double oe = ins * o_y;
+        double interest = 0.0, payment = 0.0;
+        if (y <= term && pmt != 0.0) {
+            interest = balance * r;
+            payment = pmt;
+            balance = balance - (pmt - interest);
+        }
+        const double itc_y = (y == 1) ? itc : 0.0;
+        double sta_tax = 0.0, fed_tax = 0.0;
+        if (market != 0) {
+            const double dep = depr_frac(depr_type, y, cfg.depr_sl_years) * basis;
+            sta_tax = sta * (ev - oe - interest - dep);
+            fed_tax = fed * (ev - oe - interest - dep - sta_tax);
+        }
+        const double taxsav = itc_y - sta_tax - fed_tax;
+        const double atcf = ev - oe - payment + taxsav;
+        const double cfp = ev - oe + taxsav;
+        acc += atcf * df;
+        df *= rr;
+        cum += cfp;
+        if (!paid && cum > 0.0) {
+            pb = (cfp != 0.0) ? (double)y - cum / cfp : (double)y - 0.5;
+            paid = true;
+        }
+        r_y = r_y * rate_base;
+        s_y = s_y * sys_base;
+        o_y = o_y * (1.0 + infl);
+    }
+    a.npv = -(C - debt) + acc;
+    a.payback = pb;
+    a.cost = C;
+    a.bank = bank;
+    a.power = power;
+    a.status = info & (DGEN_ST_EMPTY_EC | DGEN_ST_DEMAND);
+    return -a.npv;
+}
+
+__global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, const double* __restrict__ lo_p,
+            const double* __restrict__ hi_p, double ratio, double hours, int trace_n, dgen_swb_out S) {
+    const int64_t i = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int PH = lds_half(T.max_periods);
+    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BC_BLOCK]
+    const double q = __builtin_nan("");
+    double* const tx = (trace_n > 0 && S.trace_x) ? S.trace_x + i * trace_n : nullptr;
+    double* const tf = (trace_n > 0 && S.trace_f) ? S.trace_f + i * trace_n : nullptr;
+    for (int k = 0; k < trace_n; k++) {
+        if (tx) tx[k] = q;
+        if (tf) tf[k] = q;
+    }
+    const int t0 = A.tariff0[i];
+    const int N = A.econ_life[i];
+    int status = 0;
+    if (N < 1 || N > MAXY) status |= DGEN_ST_YEARS;
+    if (t0 < 0 || t0 >= T.n_tariffs) status |= DGEN_ST_TARIFF;
+    else if (T.tariffs[t0].flags & DGEN_ST_UNIT) status |= DGEN_ST_HOURLY_FORM;   // an agent the sizing call leaves unsized
+    double low, high;
+    if (lo_p) {
+        low = lo_p[i];
+        high = hi_p[i];
+    } else {                                                         // k_size_w's bracket (ff:440-444)
+        const double max_load = A.load_kwh[i] / T.cf_naep[A.cf_row[i]];
+        low = max_load * 0.8;
+        high = max_load * 1.25;
+    }
+    const double span = high - low;
+    const double tl = (span > 1.0 ? span : 1.0) * 1e-3;
+    const double fl_tl = floor(tl);
+    const double xatol = fl_tl < 2.0 ? 2.0 : fl_tl;
+    if (!isfinite(low) || !isfinite(high) || !(low > 0.0) || !(low < high)) status |= DGEN_ST_BOUNDS;
+    if (A.load_kwh[i] == 0.0) status |= DGEN_ST_ZERO_LOAD;
+    if (S.system_kw) S.system_kw[i] = q;
+    if (status & SWB_FATAL) {
+        const BcPoint z = {q, q, q, q, q, q, q, q, t0, 0, status};
+        swb_store(S, i, z);
+        if (S.nfev) S.nfev[i] = 0;
+        return;
+    }
+    // The members are stored whenever an evaluation becomes the search's best
+    // point (brent_bounded's own rule: the first one, then fu <= fx), so after
+    // the search they are the bits of the evaluation at the x it returns.  An
+    // evaluation that cannot be valued ends the lane: its NaN members and
+    // status are stored and every later request returns at once.
+    int cnt = 0;
+    bool dead = false;
+    double best = 0.0;
+    int nfev = 0;
+    double x_last = 0.0;
+    const double kw = brent_bounded(
+        [&](double x) __attribute__((always_inline)) {
+            if (dead) return q;
+            BcPoint a;
+            const double f = swb_point(T, A, cfg, i, batt_on, lds, PH, x, ratio, hours, a);
+            if (cnt < trace_n) {
+                if (tx) tx[cnt] = x;
+                if (tf) tf[cnt] = f;
+            }
+            dead = (a.status & SWB_FATAL) != 0;
+            if (dead || cnt == 0 || f <= best) {
+                best = f;
+                a.status |= status;
+                swb_store(S, i, a);
+            }
+            cnt += 1;
+            return f;
+        },
+        low, high, xatol, &nfev, &x_last);
+    if (S.system_kw && !dead) S.system_kw[i] = kw;
+    if (S.nfev) S.nfev[i] = cnt;
+}
 #endif  // !DGEN_TU_SEARCH
 
 }  // namespace
@@ -10223,6 +10523,69 @@ int32_t dgen_batt_curve_peak(dgen_ctx* c, const dgen_tables* T, const dgen_agent
     }
     hipLaunchKernelGGL(k_batt_curve_peak, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A,
                        *O, c->cfg, n, (int)K, c->battery, kwh, kw_pts, *out, c->bp_ws, capm, capk, dc_nq);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_size_with_batt(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, int64_t n, const double* lo,
+                            const double* hi, const dgen_swb_opt* opt, const dgen_swb_out* out, void* stream) {
+    if (!c || !T || !A || !out || n < 0) {
+        set_err("dgen_size_with_batt: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (!out->status) {
+        set_err("dgen_size_with_batt: out->status is NULL");
+        return DGEN_E_ARG;
+    }
+    if ((lo == nullptr) != (hi == nullptr)) {
+        set_err("dgen_size_with_batt: lo and hi must both be given or both be NULL");
+        return DGEN_E_ARG;
+    }
+    double ratio = 0.8, hours = 2.0;
+    int trace_n = 0;
+    if (opt) {
+        if (opt->pv_to_batt_ratio > 0.0) ratio = opt->pv_to_batt_ratio;
+        if (opt->hours > 0.0) hours = opt->hours;
+        trace_n = opt->trace_n;
+    }
+    if (trace_n < 0 || trace_n > DGEN_SWB_TRACE_MAX) {
+        set_err("dgen_size_with_batt: trace_n = %d, must be 0 .. %d", trace_n, DGEN_SWB_TRACE_MAX);
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->cf_naep || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand) || (T->n_switches > 0 && !T->switches)) {
+        set_err("dgen_size_with_batt: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    const void* cols[] = {A->load_row, A->cf_row, A->load_kwh, A->flags, A->tariff0, A->sw_storage_off,
+                          A->sw_storage_cnt, A->econ_life, A->loan_term, A->inflation, A->pv_deg, A->escalator,
+                          A->down_payment, A->tax_rate, A->real_discount, A->itc_frac, A->capex, A->capex_combined,
+                          A->batt_capex_kwh, A->ccm, A->vor};
+    for (const void* p : cols)
+        if (!p) { set_err("dgen_size_with_batt: missing agent column"); return DGEN_E_ARG; }
+    if (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1) {
+        set_err("dgen_size_with_batt: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not replayed: the daily plan under constant efficiencies only");
+        return DGEN_E_ARG;
+    }
+    const int64_t blocks = (n + BC_BLOCK - 1) / BC_BLOCK;
+    if (blocks > 0x7fffffff) {
+        set_err("dgen_size_with_batt: n = %lld exceeds the launch grid", (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    const size_t lds = (size_t)BC_PLANES * lds_half(T->max_periods) * BC_BLOCK * sizeof(double);
+    HIP_TRY(hipSetDevice(c->device));
+    if (lds > (size_t)c->lds_max) {
+        set_err("dgen_size_with_batt: %zu B of LDS for %d periods exceed the device's %d B per block", lds,
+                lds_half(T->max_periods), c->lds_max);
+        return DGEN_E_ARG;
+    }
+    if (lds > 65536)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_size_batt),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_size_batt, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A, c->cfg,
+                       n, c->battery, lo, hi, ratio, hours, trace_n, *out);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

@@ -833,6 +833,56 @@ class Engine:
         self._keep["_batt_curve"] = (e, p)    # alive until the next call (stream order)
         return res
 
+    def size_with_batt(self, batch: AgentBatch, ratio: float = 0.8, hours: float = 2.0, lo=None, hi=None,
+                       trace: int = 0, want=None) -> Dict[str, object]:
+        """PV size of `batch` on the with-battery objective --
+        dgen_size_with_batt, async on the current stream: the sizing call's
+        bounded search over the PV size x, minimising -npv of the PV+battery
+        run whose bank is sized from x (x / ratio kWh at (x / ratio) / hours
+        kW), every evaluation from (tariff0, not switched).  No outputs of a
+        sizing call are needed.  lo, hi: the bracket per agent ([n] device
+        tensors or host arrays, in the batch's device order; batch.perm maps
+        caller rows to it), both or neither; None: the sizing call's bracket.
+        trace: evaluations recorded per agent, 0 .. _lib.SWB_TRACE_MAX.
+        want: the members to compute (default all of _lib.SWB_FIELDS; status
+        always).  Returns {member: [n] device tensor}: system_kw, npv,
+        payback_raw, total_cost, bank_kwh, power_kw, bill_w_year1,
+        bill_wo_year1, lifetime_savings (float64), nfev, tariff, switched,
+        status (int32; an agent with a fatal status holds NaN), and with
+        trace > 0 trace_x, trace_f ([n, trace] float64, NaN beyond nfev).  The
+        definitions are in include/dgen_hip.h."""
+        torch = _torch()
+        want = tuple(_lib.SWB_FIELDS if want is None else want)
+        bad = [k for k in want if k not in _lib.SWB_FIELDS]
+        if bad:
+            raise ValueError(f"size_with_batt: want must name members of {_lib.SWB_FIELDS} (got {want})")
+        if "status" not in want:
+            want = want + ("status",)
+        if (lo is None) != (hi is None):
+            raise ValueError("size_with_batt: lo and hi must both be given or both be None")
+        n = batch.n
+        trace = int(trace)
+        a = b = None
+        if lo is not None:
+            a = self._to_dev(lo, torch.float64).contiguous()
+            b = self._to_dev(hi, torch.float64).contiguous()
+            if a.dim() != 1 or a.numel() != n or b.dim() != 1 or b.numel() != n:
+                raise ValueError(f"size_with_batt: lo and hi must hold one value per agent ({n}), "
+                                 f"got {tuple(a.shape)} and {tuple(b.shape)}")
+        res = {k: torch.empty(n, dtype=torch.float64 if k in _lib.SWB_F64 else torch.int32, device=self.dev)
+               for k in want}
+        so = _lib.SwbOut(**{k: _ptr(v) for k, v in res.items()})
+        if 0 < trace <= _lib.SWB_TRACE_MAX:
+            for k in ("trace_x", "trace_f"):
+                res[k] = torch.empty((n, trace), dtype=torch.float64, device=self.dev)
+                setattr(so, k, _ptr(res[k]))
+        opt = _lib.SwbOpt(float(ratio), float(hours), trace, 0)
+        _lib.check(self.lib.dgen_size_with_batt(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                                n, _ptr(a), _ptr(b), ctypes.byref(opt), ctypes.byref(so),
+                                                self.stream_handle()), "dgen_size_with_batt")
+        self._keep["_swb"] = (a, b)           # alive until the next call (stream order)
+        return res
+
     def brent_selftest(self, lo, hi, xatol, c2, x0, c1, maxn=64):
         torch = _torch()
         f = lambda v: self._to_dev(np.asarray(v, dtype=np.float64), torch.float64)

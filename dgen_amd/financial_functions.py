@@ -236,7 +236,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                 hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
                 keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
-                bill_metrics: bool = False, batt_sizing=None):
+                bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -257,7 +257,10 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     bill_metrics: each sub-batch also bills its three cases month by month on
     the device (bill_metrics.COLUMNS, per-agent values: the bits of one call).
     batt_sizing: each sub-batch also runs the battery size what-if on the
-    device (batt_sizing.COLUMNS, per-agent values: the bits of one call)."""
+    device (batt_sizing.COLUMNS, per-agent values: the bits of one call).
+    pv_batt_sizing: each sub-batch also sizes its PV on the with-battery
+    objective (batt_sizing.CO_COLUMNS, per-agent values: the bits of one
+    call)."""
     n = len(cols["load_kwh"])
     if max_rows is None:
         max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics, bill_metrics=bill_metrics)
@@ -265,7 +268,8 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     import torch
     try:
         return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
-                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing,
+                                pv_batt_sizing)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -275,16 +279,18 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
         torch.cuda.empty_cache()
         return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
                            grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw,
-                           batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing)
+                           batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing,
+                           pv_batt_sizing=pv_batt_sizing)
 
 
 def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
                      grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None,
-                     batt_metrics: bool = False, bill_metrics: bool = False, batt_sizing=None):
+                     batt_metrics: bool = False, bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
     n = len(cols["load_kwh"])
     if n <= max_rows:
         return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
-                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing)
+                                grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing,
+                                pv_batt_sizing)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -302,7 +308,7 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
                                       grid_metrics=grid_metrics, keep_planes=keep_planes,
                                       fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi],
                                       batt_metrics=batt_metrics, bill_metrics=bill_metrics,
-                                      batt_sizing=batt_sizing))
+                                      batt_sizing=batt_sizing, pv_batt_sizing=pv_batt_sizing))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -325,6 +331,10 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
     if batt_sizing is not None:
         from .batt_sizing import COLUMNS as SIZING_COLUMNS
         for name in SIZING_COLUMNS:
+            o[name] = np.concatenate([p[name] for p in parts])
+    if pv_batt_sizing is not None:
+        from .batt_sizing import CO_COLUMNS
+        for name in CO_COLUMNS:
             o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
         if not keep_planes:
@@ -349,7 +359,7 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                      hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True,
                      fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
-                     bill_metrics: bool = False, batt_sizing=None):
+                     bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
     """Size the batch in one device call (fixed_kw: evaluate caller row i at
     fixed_kw[i] kW instead, Engine.evaluate); net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
@@ -365,7 +375,9 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     bill_metrics: o also holds bill_metrics.COLUMNS, the annual bill breakdown
     of the three cases under tariff_final (Engine.bill_months, caller order).
     batt_sizing: o also holds batt_sizing.COLUMNS, the best of the spec's
-    battery banks per agent (Engine.batt_curve, caller order)."""
+    battery banks per agent (Engine.batt_curve, caller order).
+    pv_batt_sizing: o also holds batt_sizing.CO_COLUMNS, the PV size on the
+    with-battery objective (Engine.size_with_batt, caller order)."""
     import time
     import torch
     from .attachment import state_hourly
@@ -403,6 +415,10 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     if batt_sizing is not None:
         from .batt_sizing import annual_columns as sizing_columns
         bsz = sizing_columns(eng, batch, out, batt_sizing)
+    pvb = None
+    if pv_batt_sizing is not None:
+        from .batt_sizing import co_size_columns
+        pvb = co_size_columns(eng, batch, out, pv_batt_sizing)
     gm = None
     if grid_metrics:
         from .grid_metrics import annual_columns
@@ -434,6 +450,8 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         o.update(blm)
     if bsz is not None:
         o.update(bsz)
+    if pvb is not None:
+        o.update(pvb)
     if timing is not None:
         timing.update(upload_s=t1 - t0, device_s=t2 - t1, download_s=time.perf_counter() - t2)
     return o
@@ -568,7 +586,7 @@ def _fixed_kw_values(df: pd.DataFrame, fixed_kw) -> np.ndarray:
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
                grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
-               bill_metrics: bool = False, batt_sizing=None):
+               bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -639,11 +657,27 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     net-billing tariffs; dgen_batt_curve_net), which otherwise carry
     batt_opt_point = -1; its key "peak_billing": True those whose tariff bills
     demand charges or has kWh/kW tier units (dgen_batt_curve_peak).  None (the
-    default) leaves the frame unchanged."""
+    default) leaves the frame unchanged.  pv_batt_sizing: True, or a dict with
+    "ratio" and / or "hours" (batt_sizing.co_size_spec; the reference's 0.8 and
+    2.0 otherwise) -- adds the eight columns batt_sizing.CO_COLUMNS: the PV size
+    that maximises the with-battery NPV when the bank is sized from it (x /
+    ratio kWh at hours; Engine.size_with_batt, dgen_size_with_batt), searched
+    over the sizing call's bracket after each sub-batch's sizing or evaluation:
+    pvb_opt_kw, pvb_opt_kwh, pvb_opt_batt_kw (the installed bank), pvb_opt_npv,
+    pvb_opt_payback, pvb_opt_nfev, pvb_opt_status and pvb_opt_npv_gain (over
+    the sizing call's npv_pv_batt; NaN where either is invalid).  Tariffs the
+    search does not cover carry ST_HOURLY_FORM and NaN.  No plane is read: the
+    same bits in every hourly mode and sub-batching.  None (the default) leaves
+    the frame unchanged."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
     fixed = None if fixed_kw is None else _fixed_kw_values(df, fixed_kw)
+    if pv_batt_sizing is False:
+        pv_batt_sizing = None
+    if pv_batt_sizing is not None:
+        from .batt_sizing import co_size_spec
+        co_size_spec(pv_batt_sizing)           # a bad spec raises before anything is launched
     t0 = time.perf_counter()
     src = _source(con)
     src.ensure_frame(df)
@@ -654,7 +688,8 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     o = _run_device(b, cols, src, dev_t, net_weights, hourly_async=hourly in ("lazy", "array", "list"),
                     hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
                     keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed,
-                    batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing)
+                    batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing,
+                    pv_batt_sizing=pv_batt_sizing)
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -735,6 +770,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
         from .batt_sizing import COLUMNS as SIZING_COLUMNS
         for name in SIZING_COLUMNS:
             out[name] = o[name]
+    if pv_batt_sizing is not None:
+        from .batt_sizing import CO_COLUMNS
+        for name in CO_COLUMNS:
+            out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:
         # download_wait_s: time the frame assembly waited for the hourly planes
@@ -746,7 +785,7 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
                hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
                grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
-               bill_metrics: bool = False, batt_sizing=None):
+               bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
     agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
     grid_metrics: size_frame's 18 per-agent grid-exchange columns.  fixed_kw:
@@ -754,7 +793,9 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     evaluated at those sizes instead of being sized).  batt_metrics:
     size_frame's per-agent battery dispatch columns (batt_diag_*).
     bill_metrics: size_frame's 18 per-agent year-1 bill columns (bill_*).
-    batt_sizing: size_frame's points spec (the seven batt_opt_* columns)."""
+    batt_sizing: size_frame's points spec (the seven batt_opt_* columns).
+    pv_batt_sizing: size_frame's spec of the PV size on the with-battery
+    objective (the eight pvb_opt_* columns)."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -769,7 +810,7 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
                            net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics,
                            fixed_kw=fixed_kw, batt_metrics=batt_metrics, bill_metrics=bill_metrics,
-                           batt_sizing=batt_sizing)
+                           batt_sizing=batt_sizing, pv_batt_sizing=pv_batt_sizing)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

@@ -1148,6 +1148,82 @@ int32_t dgen_batt_curve_peak(dgen_ctx* ctx, const dgen_tables* tables, const dge
                              const double* kw_pts, const dgen_batt_peak_opt* opt,
                              const dgen_batt_curve_out* out, void* stream);
 
+/* PV sizing on the with-battery objective (additive to ABI 14): the bounded
+ * scalar search of the sizing call (scipy's minimize_scalar(method='bounded'),
+ * op for op) over the PV size x, minimising the reference's perf_with_batt
+ *     f(x) = -npv of calc_system_performance(x, en_batt=True)
+ * (financial_functions.py:427-435), whose battery is sized from x.  The
+ * reference builds this objective and evaluates it once, at the PV-only
+ * optimum; it never searches on it, so there is no reference path to
+ * reproduce.  f is therefore defined as a function of x alone: every
+ * evaluation starts from (tariff0[i], not switched), dgen_objective_curve's
+ * convention, and the storage rate switch's stickiness is not carried from one
+ * evaluation to the next.  A path-dependent objective could not be checked
+ * point by point; this one is the dgen_batt_curve point with
+ *     sized.system_kw = x, sized.tariff_final = tariff0, sized.switched = 0,
+ *     kwh = x / ratio, kw_pts = (x / ratio) / hours
+ * bit for bit, in every member: bank and power (battery_model_sizing),
+ * dispatch replay, storage rate switch on the bank, (month, period) bins, the
+ * N years' bills, cost = (capex_combined x x + batt_capex_kwh x bank x 0.7) x
+ * ccm + otc, Cashloan and the forward-sum NPV, each as defined under
+ * dgen_batt_curve.
+ * opt: pv_to_batt_ratio (<= 0 or NaN: 0.8, ff:140), hours (<= 0 or NaN: 2.0,
+ * ff:141), trace_n in 0 .. DGEN_SWB_TRACE_MAX; opt NULL: 0.8, 2.0, no trace.
+ * Bracket: lo and hi are device arrays [n], both given or both NULL.  NULL:
+ * the sizing call's bracket bit for bit, max_load = load_kwh / cf_naep[cf_row],
+ * lo = 0.8 x max_load, hi = 1.25 x max_load (ff:440-443).  In both cases
+ * xatol = max(2, floor(max(1, hi - lo) x 1e-3)) (ff:444).  A bracket that is
+ * not finite, has lo <= 0 or has lo >= hi gives DGEN_ST_BOUNDS; load_kwh == 0
+ * adds DGEN_ST_ZERO_LOAD as in the sizing call.
+ * Members, each [n], any may be NULL except status: system_kw is the x the
+ * search returns (always an evaluated point), nfev its number of evaluations;
+ * npv, payback_raw, total_cost, bank_kwh, power_kw, bill_w_year1,
+ * bill_wo_year1, lifetime_savings, tariff and switched are the bits of the
+ * evaluation at system_kw (so npv = -min over the evaluations of f).
+ * trace_x, trace_f: [n][trace_n] agent-major, evaluation k's x and f(x) for
+ * k < min(nfev, trace_n), NaN beyond; either may be NULL.
+ * Covered tariffs are dgen_batt_curve's: metering options 0, 1 and 4, tier
+ * units 0 and 2, no demand charge billed.  Status: DGEN_ST_YEARS (economic
+ * life outside 1 .. DGEN_MAXY) and DGEN_ST_TARIFF (tariff0 outside the
+ * table; a switch to an index outside it or to a tariff beyond
+ * tables->max_periods) as dgen_batt_curve assigns them; an agent whose tariff0
+ * carries DGEN_ST_UNIT gets DGEN_ST_HOURLY_FORM without an evaluation.  When
+ * the tariff after the switch of any evaluation bills hourly imports (options
+ * 2, 3), bills demand charges or has kWh/kW tier units, the agent gets
+ * DGEN_ST_HOURLY_FORM, tariff and switched of that evaluation, and nfev counts
+ * the evaluations up to and including it: no later evaluation of that agent
+ * walks the year.  Every double member of an agent with DGEN_ST_BOUNDS,
+ * _TARIFF, _YEARS or _HOURLY_FORM is NaN (its trace keeps what was recorded).
+ * Other agents carry DGEN_ST_ZERO_LOAD and the DGEN_ST_EMPTY_EC / _DEMAND flags
+ * of tariff0 and of the tariff billed at system_kw, or 0.
+ * After dgen_set_battery(ctx, 0) every bank is 0 and the search runs on the
+ * PV-only bills with capex_combined.  batt_update_hours == 1 or
+ * batt_loss_model == 1, trace_n out of range, one of lo / hi NULL and
+ * out->status NULL return DGEN_E_ARG.  Agent i's results do not depend on n or
+ * on its neighbours; no atomics, no cross-lane sums, no workspace and no
+ * dgen_outputs: run-to-run identical.  One lane per agent walks the year once
+ * per evaluation; the kernel keeps 26 x max_periods x 512 B of LDS per 64
+ * agents.                                                                     */
+#define DGEN_SWB_TRACE_MAX 32
+
+typedef struct {
+    double  pv_to_batt_ratio;   /* desired_kwh = x / ratio; <= 0 or NaN: 0.8 (ff:140) */
+    double  hours;              /* desired_kw = desired_kwh / hours; <= 0 or NaN: 2.0 (ff:141) */
+    int32_t trace_n;            /* evaluations recorded per agent, 0 .. DGEN_SWB_TRACE_MAX */
+    int32_t pad;
+} dgen_swb_opt;                 /* NULL: 0.8, 2.0, no trace */
+
+typedef struct {                /* each [n]; any may be NULL except status */
+    double  *system_kw, *npv, *payback_raw, *total_cost, *bank_kwh, *power_kw,
+            *bill_w_year1, *bill_wo_year1, *lifetime_savings;
+    int32_t *nfev, *tariff, *switched, *status;
+    double  *trace_x, *trace_f; /* [n][trace_n] agent-major, unused entries NaN; may be NULL */
+} dgen_swb_out;
+
+int32_t dgen_size_with_batt(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents, int64_t n,
+                            const double* lo, const double* hi, const dgen_swb_opt* opt,
+                            const dgen_swb_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
