@@ -174,11 +174,21 @@ def export_weights(engine, customers_in_bin, number_of_adopters, batt_kw_cum_las
     return tuple(w)
 
 
+def _check_weights(eng, weights, what):
+    """The kernels read each weight as n doubles: anything else would be read
+    out of bounds (float32) or not at all (a host tensor)."""
+    import torch
+    for w in weights:
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or w.device != eng.dev:
+            raise TypeError(f"{what}: weights must be float64 tensors on the engine's device")
+
+
 def state_hourly(engine, planes, weights, idx, seg_off):
     """k_state_hourly: planes = (baseline, pvonly, with_batt) device tensors,
     float32 or float64 in dgen_size_agents' hour-quad tiles [n_hours / 4, n, 4]
     (the sizing outputs in place; engine.tile_hourly makes them from
-    [n_hours, n]) or float64 [n_hours, n]; weights from export_weights(), idx: plane column of
+    [n_hours, n]) or float64 [n_hours, n]; weights from export_weights() (float64 tensors on the
+    engine's device, one value per plane column: TypeError otherwise), idx: plane column of
     each group member (None: identity), seg_off [S+1].  Returns a [S, n_hours]
     float64 device tensor in MW."""
     import torch
@@ -200,6 +210,9 @@ def state_hourly(engine, planes, weights, idx, seg_off):
     else:
         raise ValueError("state_hourly: float32 planes must be hour-quad tiles [n_hours/4, n, 4]; "
                          "float64 planes tiles or [n_hours, n]")
+    if len(weights) != 3:
+        raise ValueError("state_hourly: three weights (w_pvo, w_batt, w_non)")
+    _check_weights(eng, weights, "state_hourly")
     if any(w.numel() != n for w in weights):
         raise ValueError("state_hourly: one weight per plane column")
     so = np.asarray(seg_off, dtype=np.int64)
@@ -271,12 +284,15 @@ def state_hourly_rows(engine, batch, c_out, with_batt, weights, idx, seg_off):
     state_hourly; returns a [S, 8760] float64 device tensor in MW."""
     import torch
     eng = _engine(engine)
+    if len(weights) != 3:
+        raise ValueError("state_hourly_rows: three weights (w_pvo, w_batt, w_non)")
+    _check_weights(eng, weights, "state_hourly_rows")
     if with_batt.dtype != torch.float32 or with_batt.dim() != 3 or with_batt.shape[2] != 4:
         raise ValueError("state_hourly_rows: the with-battery plane is float32 hour-quad tiles [8760/4, n, 4]")
     nh, n = with_batt.shape[0] * 4, with_batt.shape[1]
     if nh != NH_FULL or n != batch.n:
         raise ValueError("state_hourly_rows: one 8760-h plane column per batch agent")
-    w = [x.contiguous() for x in weights]
+    w =[x.contiguous() for x in weights]
     if any(x.numel() != n for x in w):
         raise ValueError("state_hourly_rows: one weight per agent")
     so = np.asarray(seg_off, dtype=np.int64)

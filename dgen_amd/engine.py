@@ -619,7 +619,8 @@ class Engine:
     def segment_sums(self, v1, seg_off, w1=None, v2=None, w2=None):
         """Weighted sums of k planes of n agents over contiguous segments
         (device, deterministic order).  v1/v2: [k, n] float32/float64 device
-        tensors; seg_off: [S+1] offsets; returns a [S, k] float64 device tensor."""
+        tensors of one shape; w1 / w2: [n] weights (w1 None: 1; v2 needs w2);
+        seg_off: [S+1] offsets; returns a [S, k] float64 device tensor."""
         torch = _torch()
         if v1.dim() == 1:
             v1 = v1.view(1, -1)
@@ -628,6 +629,13 @@ class Engine:
         f32 = v1.dtype == torch.float32
         if v1.dtype not in (torch.float32, torch.float64) or (v2 is not None and v2.dtype != v1.dtype):
             raise TypeError("segment_sums: values must be float32 or float64 (same dtype)")
+        if v2 is not None and v2.shape != v1.shape:
+            raise ValueError("segment_sums: v2 must have v1's shape")
+        if v2 is not None and w2 is None:
+            raise ValueError("segment_sums: v2 needs its weights w2")
+        for w in (w1, w2):                     # the kernel reads n doubles of each
+            if w is not None and (np.ndim(w) != 1 or len(w) != n):
+                raise ValueError("segment_sums: one weight per agent")
         so = self._to_dev(seg_off, torch.int64)
         if so.numel() < 1 or int(so[0].item()) < 0 or int(so[-1].item()) > n or \
                 bool((so[1:] < so[:-1]).any().item()):
