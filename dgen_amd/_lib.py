@@ -204,6 +204,12 @@ class SwbOut(ctypes.Structure):
     _fields_ = [(name, _vp) for name in SWB_FIELDS] + [("trace_x", _vp), ("trace_f", _vp)]
 
 
+class SwbNetOpt(ctypes.Structure):
+    """dgen_swb_net_opt: cap = the mixed hours a month's list holds per agent (<= 0: NB_CAPM), max_blocks =
+    the persistent blocks of the launch (<= 0: the blocks resident on the device)."""
+    _fields_ = [("cap", _i32), ("max_blocks", _i32)]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -223,7 +229,7 @@ EXPORTED = [
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
     "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
-    "dgen_size_with_batt",
+    "dgen_size_with_batt", "dgen_size_with_batt_net",
 ]
 
 
@@ -329,6 +335,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_size_with_batt.restype = _i32
     L.dgen_size_with_batt.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _i64, _vp, _vp,
                                       ctypes.POINTER(SwbOpt), ctypes.POINTER(SwbOut), _vp]
+    L.dgen_size_with_batt_net.restype = _i32
+    L.dgen_size_with_batt_net.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _i64, _vp, _vp,
+                                          ctypes.POINTER(SwbOpt), ctypes.POINTER(SwbNetOpt), ctypes.POINTER(SwbOut),
+                                          _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

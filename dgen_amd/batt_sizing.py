@@ -26,9 +26,12 @@ list overflow.
 
 All of the above hold the PV size at kW*.  ``Engine.size_with_batt``
 (dgen_size_with_batt) instead searches the PV size x on the with-battery
-objective, the bank sized from x (x / ratio kWh at hours):
+objective, the bank sized from x (x / ratio kWh at hours); net=True (the spec
+key "net_billing": True) adds dgen_size_with_batt_net on the same buffers: the
+agents whose evaluations reach options 2 and 3 are searched too:
 
     co_size_spec(spec)                           size_frame's pv_batt_sizing spec as (ratio, hours)
+    co_size_options(spec)                        its net-billing settings (Engine.size_with_batt's keywords)
     co_size_summarize(res, npv_ref, status_ref)  the CO_COLUMNS of a search result
     co_size_columns(engine, batch, out, spec)    the per-agent columns of the drop-in switch
                                                  (financial_functions.size_frame(pv_batt_sizing=spec))
@@ -252,18 +255,45 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
 def co_size_spec(spec) -> Tuple[float, float]:
     """size_frame's pv_batt_sizing spec as (ratio, hours): True for the
     reference's constants (0.8, 2.0), or a dict with "ratio" and / or "hours";
-    both must be finite and positive."""
+    both must be finite and positive.  The dict's "net_billing", "net_cap" and
+    "net_blocks" keys are not part of the pair (co_size_options(spec))."""
     if spec is True:
         return REF_PV_TO_BATT, REF_HOURS
     if not isinstance(spec, dict):
         raise ValueError(f"pv_batt_sizing: True or a dict with \"ratio\" / \"hours\" (got {spec!r})")
-    bad = set(spec) - {"ratio", "hours"}
+    bad = set(spec) - {"ratio", "hours", "net_billing", "net_cap", "net_blocks"}
     if bad:
         raise ValueError(f"pv_batt_sizing: unknown keys {sorted(bad)}")
     r, h = float(spec.get("ratio", REF_PV_TO_BATT)), float(spec.get("hours", REF_HOURS))
     if not (np.isfinite(r) and r > 0.0 and np.isfinite(h) and h > 0.0):
         raise ValueError(f"pv_batt_sizing: ratio and hours must be finite and positive (got {r}, {h})")
     return r, h
+
+
+def co_size_options(spec) -> Dict[str, object]:
+    """Engine.size_with_batt's net keywords of a pv_batt_sizing spec: none for
+    True or a dict without "net_billing": True (the engine then sees the call
+    it always saw), else {"net": True} with "net_cap" (1 .. _lib.NB_CAPM mixed
+    hours a month) and "net_blocks" (>= 1 persistent blocks) where the spec
+    names them.  "net_billing" must be a bool, the other two ints (None: the
+    default); they are checked even when net billing is off."""
+    co_size_spec(spec)
+    if spec is True:
+        return {}
+    net = spec.get("net_billing", False)
+    if not isinstance(net, (bool, np.bool_)):
+        raise ValueError(f"pv_batt_sizing: net_billing must be a bool (got {net!r})")
+    kw = {}
+    for key, name, top in (("net_cap", "net_cap", _lib.NB_CAPM), ("net_blocks", "net_blocks", None)):
+        v = spec.get(key)
+        if v is None:
+            continue
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"pv_batt_sizing: {key} must be an int (got {v!r})")
+        if v < 1 or (top is not None and v > top):
+            raise ValueError(f"pv_batt_sizing: {key} must be " + (f"1 .. {top}" if top else ">= 1") + f" (got {v})")
+        kw[name] = int(v)
+    return {"net": True, **kw} if net else {}
 
 
 def co_size_summarize(res: Dict[str, object], npv_ref, status_ref) -> Dict[str, object]:
@@ -296,11 +326,12 @@ def co_size_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     bracket at co_size_spec(spec), reduced by co_size_summarize() against the
     npv_pv_batt and status of the sized output dict `out`.  float64, except
     pvb_opt_nfev and pvb_opt_status (int64).  Only these [n] vectors cross to
-    the host."""
+    the host.  With "net_billing": True in the spec the agents on net-billing
+    tariffs are searched too (dgen_size_with_batt_net; co_size_options(spec))."""
     import torch
     r, h = co_size_spec(spec)
     d = engine.size_with_batt(batch, r, h, want=("system_kw", "bank_kwh", "power_kw", "npv", "payback_raw", "nfev",
-                                                 "status"))
+                                                 "status"), **co_size_options(spec))
     s = co_size_summarize(d, out["npv_pv_batt"], out["status"])
     inv = _inverse(engine, batch.perm)
     res = {}

@@ -842,7 +842,8 @@ class Engine:
         return res
 
     def size_with_batt(self, batch: AgentBatch, ratio: float = 0.8, hours: float = 2.0, lo=None, hi=None,
-                       trace: int = 0, want=None) -> Dict[str, object]:
+                       trace: int = 0, want=None, net: bool = False, net_cap: Optional[int] = None,
+                       net_blocks: Optional[int] = None) -> Dict[str, object]:
         """PV size of `batch` on the with-battery objective --
         dgen_size_with_batt, async on the current stream: the sizing call's
         bounded search over the PV size x, minimising -npv of the PV+battery
@@ -857,8 +858,16 @@ class Engine:
         payback_raw, total_cost, bank_kwh, power_kw, bill_w_year1,
         bill_wo_year1, lifetime_savings (float64), nfev, tariff, switched,
         status (int32; an agent with a fatal status holds NaN), and with
-        trace > 0 trace_x, trace_f ([n, trace] float64, NaN beyond nfev).  The
-        definitions are in include/dgen_hip.h."""
+        trace > 0 trace_x, trace_f ([n, trace] float64, NaN beyond nfev).
+        net=True follows with dgen_size_with_batt_net on the same buffers and
+        stream: the agents whose tariff0 or storage rows reach metering
+        options 2 and 3 are searched with those evaluations billed hourly
+        instead of ending flagged _lib.ST_HOURLY_FORM; every other agent keeps
+        the first call's bits.  net_cap: the mixed hours a month may hold per
+        agent (default _lib.NB_CAPM; an evaluation beyond it ends the agent
+        flagged); net_blocks: a cap on the launch's persistent blocks and so
+        on its workspace (default: the blocks resident on the device; results
+        do not depend on it).  The definitions are in include/dgen_hip.h."""
         torch = _torch()
         want = tuple(_lib.SWB_FIELDS if want is None else want)
         bad = [k for k in want if k not in _lib.SWB_FIELDS]
@@ -888,6 +897,12 @@ class Engine:
         _lib.check(self.lib.dgen_size_with_batt(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
                                                 n, _ptr(a), _ptr(b), ctypes.byref(opt), ctypes.byref(so),
                                                 self.stream_handle()), "dgen_size_with_batt")
+        if net:
+            no = _lib.SwbNetOpt(0 if net_cap is None else int(net_cap), 0 if net_blocks is None else int(net_blocks))
+            _lib.check(self.lib.dgen_size_with_batt_net(self.ctx, ctypes.byref(self.tables),
+                                                        ctypes.byref(batch.c_agents), n, _ptr(a), _ptr(b),
+                                                        ctypes.byref(opt), ctypes.byref(no), ctypes.byref(so),
+                                                        self.stream_handle()), "dgen_size_with_batt_net")
         self._keep["_swb"] = (a, b)           # alive until the next call (stream order)
         return res
 

@@ -666,7 +666,11 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     pvb_opt_kw, pvb_opt_kwh, pvb_opt_batt_kw (the installed bank), pvb_opt_npv,
     pvb_opt_payback, pvb_opt_nfev, pvb_opt_status and pvb_opt_npv_gain (over
     the sizing call's npv_pv_batt; NaN where either is invalid).  Tariffs the
-    search does not cover carry ST_HOURLY_FORM and NaN.  No plane is read: the
+    search does not cover carry ST_HOURLY_FORM and NaN; the dict's key
+    "net_billing": True also searches the agents whose tariff bills hourly
+    imports (metering options 2 and 3: every CA agent and the net-billing
+    tariffs; dgen_size_with_batt_net), with "net_cap" and "net_blocks" that
+    entry's options (batt_sizing.co_size_options).  No plane is read: the
     same bits in every hourly mode and sub-batching.  None (the default) leaves
     the frame unchanged."""
     import time
@@ -676,8 +680,8 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     if pv_batt_sizing is False:
         pv_batt_sizing = None
     if pv_batt_sizing is not None:
-        from .batt_sizing import co_size_spec
-        co_size_spec(pv_batt_sizing)           # a bad spec raises before anything is launched
+        from .batt_sizing import co_size_options
+        co_size_options(pv_batt_sizing)        # a bad spec raises before anything is launched
     t0 = time.perf_counter()
     src = _source(con)
     src.ensure_frame(df)

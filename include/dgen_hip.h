@@ -68,9 +68,11 @@ extern "C" {
 #define DGEN_ST_ZERO_LOAD    0x40  /* load_kwh == 0: reference divides by zero (ff:549)*/
 #define DGEN_ST_DEMAND       0x80  /* demand-charge mat outside SSC's / the record's   */
                                    /* limits (month, period, tier numbering)          */
-#define DGEN_ST_HOURLY_FORM  0x100 /* dgen_batt_curve only (no other entry sets it):  */
+#define DGEN_ST_HOURLY_FORM  0x100 /* dgen_batt_curve and dgen_size_with_batt only:    */
                                    /* the point's tariff bills hourly imports, demand  */
-                                   /* charges or kWh/kW tiers, which it does not cover */
+                                   /* charges or kWh/kW tiers, which they do not cover. */
+                                   /* After the _net / _peak fill-ins of the curve, or  */
+                                   /* dgen_size_with_batt_net: see those entries' text  */
 
 /* Engine configuration: the PySAM config defaults the reference never sets
  * (CustomGenerationBattery{Residential,Commercial}, ff:59-80) plus the
@@ -1203,7 +1205,12 @@ int32_t dgen_batt_curve_peak(dgen_ctx* ctx, const dgen_tables* tables, const dge
  * on its neighbours; no atomics, no cross-lane sums, no workspace and no
  * dgen_outputs: run-to-run identical.  One lane per agent walks the year once
  * per evaluation; the kernel keeps 26 x max_periods x 512 B of LDS per 64
- * agents.                                                                     */
+ * agents.
+ * dgen_size_with_batt_net (below), called next on the same buffers, searches
+ * the agents this entry ends on options 2 and 3.  After both calls
+ * DGEN_ST_HOURLY_FORM is left on an agent whose tariff0 carries DGEN_ST_UNIT,
+ * one with an evaluation on billed demand charges or kWh/kW tier units, and
+ * one whose net-billing month overflowed that entry's cap.                    */
 #define DGEN_SWB_TRACE_MAX 32
 
 typedef struct {
@@ -1223,6 +1230,77 @@ typedef struct {                /* each [n]; any may be NULL except status */
 int32_t dgen_size_with_batt(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents, int64_t n,
                             const double* lo, const double* hi, const dgen_swb_opt* opt,
                             const dgen_swb_out* out, void* stream);
+
+/* The net-billing tariffs of that search (additive to ABI 14): the agents
+ * dgen_size_with_batt ends with DGEN_ST_HOURLY_FORM because an evaluation's
+ * tariff bills hourly imports -- metering options 2 and 3, with the period
+ * sell rate or the hourly TS sell rate.  The entry fills in: called after
+ * dgen_size_with_batt with the same lo, hi and opt on the same out buffers and
+ * stream it writes its candidates in full and nothing else.  ctx, tables,
+ * agents, n, lo, hi, opt, out and stream are dgen_size_with_batt's.
+ * Candidates are decided from the tables and the agent columns alone (out is
+ * not read).  Agent i is a candidate when all of these hold:
+ *   - its bracket (lo, hi, or the default bracket when both are NULL) is valid
+ *     under dgen_size_with_batt's rules, bit for bit;
+ *   - its economic life is in 1 .. DGEN_MAXY;
+ *   - tariff0[i] is inside the table and does not carry DGEN_ST_UNIT;
+ *   - tariff0[i], or the tariff of at least one of its sw_storage rows whose
+ *     index is inside the table, has metering option 2 or 3.
+ * Every other agent is not written at all: no member, no status, no trace row
+ * (a batch without such tariffs leaves at that check); an agent the first call
+ * valued and that cannot reach net billing keeps its bits.
+ * A candidate runs dgen_size_with_batt's search: the same bounded minimiser,
+ * xatol by ff:444, every evaluation from (tariff0, not switched), ratio, hours
+ * and trace_n from opt.  f(x) = -npv takes the form of the tariff after the
+ * storage rate switch on that evaluation's bank:
+ *   bins form (options 0, 1, 4; tier units 0, 2; no demand charge billed):
+ *       the dgen_batt_curve point, bit for bit, as in dgen_size_with_batt;
+ *   options 2 or 3, tier unit 0 or 2, no demand charge billed:
+ *       the dgen_batt_curve_net point at nopt->cap, bit for bit, the TS sell
+ *       rate included,
+ * in both cases with sized.system_kw = x, sized.tariff_final = tariff0,
+ * sized.switched = 0, kwh = x / ratio, kw_pts = kwh / hours.  One search may be
+ * billed under both forms when a storage row's edge lies between the banks of
+ * the bracket's ends.
+ * An evaluation ends the agent when the tariff after the switch bills demand
+ * charges or has kWh/kW tier units, is outside the table or beyond
+ * tables->max_periods (this one adds DGEN_ST_TARIFF), or has a month with more
+ * than cap mixed hours.  dgen_size_with_batt's rule for such a lane holds: NaN
+ * in every double member, DGEN_ST_HOURLY_FORM, tariff and switched of that
+ * evaluation, nfev up to and including it; no later request walks the year.
+ * Nothing is stored past cap.
+ * Every candidate is written in full by dgen_size_with_batt's rule (the
+ * members of the evaluation at system_kw, nfev, the trace rows NaN beyond
+ * nfev, DGEN_ST_ZERO_LOAD and the DGEN_ST_EMPTY_EC / _DEMAND flags of tariff0
+ * and of the tariff billed at system_kw), so a candidate whose evaluations were
+ * all of the bins form gets the bits the first call wrote.  NULL members are
+ * not written; status must be given.
+ * nopt->cap: the mixed hours a month's list holds per agent, 1 ..
+ * DGEN_NB_CAPM (NULL or cap <= 0: DGEN_NB_CAPM; above it: DGEN_E_ARG).
+ * nopt->max_blocks: a positive value caps the persistent blocks of the launch
+ * and so the workspace; NULL or <= 0: the blocks resident on the device.
+ * Results do not depend on it.  The lists live in dgen_batt_curve_net's
+ * ctx-owned workspace, sized by the blocks, not by n: per block 51,200 B of
+ * per-year accumulators and cap x 1024 B of entries (508 MB at the resident
+ * count of an MI355X and the default cap), grown on demand and freed by
+ * dgen_close; calls on one ctx must be stream-ordered.  One lane per
+ * candidate walks the year once per evaluation; every evaluation starts its
+ * lists and accumulators afresh.  Agent i's results do not depend on n, on its
+ * neighbours or on the blocks; no atomics, no cross-lane traffic: run-to-run
+ * identical.  The kernel keeps the larger of the two forms' layouts, 26 x
+ * max_periods x 512 B of LDS per 64 agents.
+ * Argument errors are dgen_size_with_batt's (trace_n out of range, one of
+ * lo / hi NULL, out->status NULL, batt_update_hours == 1 or
+ * batt_loss_model == 1: DGEN_E_ARG); after dgen_set_battery(ctx, 0) every bank
+ * is 0 and the search runs on the PV-only hourly bills.
+ * After both calls DGEN_ST_HOURLY_FORM means: tariff0 carries DGEN_ST_UNIT, an
+ * evaluation met billed demand charges or kWh/kW tier units, or a month's
+ * mixed list overflowed cap.                                                  */
+typedef struct { int32_t cap; int32_t max_blocks; } dgen_swb_net_opt;   /* NULL or <= 0: the defaults */
+
+int32_t dgen_size_with_batt_net(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents, int64_t n,
+                                const double* lo, const double* hi, const dgen_swb_opt* opt,
+                                const dgen_swb_net_opt* nopt, const dgen_swb_out* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,15 @@ times (ms), the nfev statistics, the yardstick and the ratio to it.
 
 --wide F: the bracket's upper end x F (explicit lo / hi): longer searches than
 the default bracket's, which for a residential agent spans little more than
-the tolerance's floor of 2 kW."""
+the tolerance's floor of 2 kW.
+
+--net: the net-billing fill-in instead, on ca_res_storage (200 k agents unless
+--agents is given), every agent on metering option 2:
+  dgen_batt_curve_net, K = 1   alone on the buffers dgen_batt_curve filled
+  dgen_size_with_batt_net      alone on the buffers dgen_size_with_batt filled
+  both search calls            as Engine.size_with_batt(net=True) issues them
+with the same yardstick from the fill-in's nfev: the K = 1 net time x the mean
+over the waves of the wave's largest nfev."""
 import argparse
 import json
 import os
@@ -22,12 +30,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--agents", type=int, default=1_000_000)
-    ap.add_argument("--config", default="res_1m_nem_tou")
+    ap.add_argument("--agents", type=int, default=None)
+    ap.add_argument("--config", default=None)
+    ap.add_argument("--net", action="store_true")
     ap.add_argument("--wide", type=float, default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
     args = ap.parse_args()
+    if args.config is None:
+        args.config = "ca_res_storage" if args.net else "res_1m_nem_tou"
+    if args.agents is None:
+        args.agents = 200_000 if args.net else 1_000_000
     import numpy as np
     import torch
     from dgen_amd import _lib
@@ -67,8 +80,12 @@ def main():
         return float(np.median(ms)), float(min(ms)), float(max(ms))
 
     want = ("npv", "payback_raw", "bank_kwh", "power_kw", "status")
-    c1 = timed(lambda: eng.batt_curve(batch, out, one, want=want))
     swant = ("system_kw",) + want + ("nfev",)
+    if args.net:
+        net_mode(args, eng, batch, out, one, lo, hi, want, swant, timed, pop)
+        eng.close()
+        return
+    c1 = timed(lambda: eng.batt_curve(batch, out, one, want=want))
     sw = timed(lambda: eng.size_with_batt(batch, lo=lo, hi=hi, want=swant))
     r = eng.size_with_batt(batch, lo=lo, hi=hi, want=("nfev", "status"))
     torch.cuda.synchronize()
@@ -86,6 +103,54 @@ def main():
                       "min_max_ms": {"k1": c1[1:], "size_with_batt": sw[1:]},
                       "agents_flagged": int(((st & fatal) != 0).sum())}))
     eng.close()
+
+
+def net_mode(args, eng, batch, out, one, lo, hi, want, swant, timed, pop):
+    import ctypes
+    import numpy as np
+    import torch
+    from dgen_amd import _lib
+    n = batch.n
+    args_c = (eng.ctx, ctypes.byref(eng.tables), ctypes.byref(batch.c_agents))
+    # dgen_batt_curve_net alone, on the members dgen_batt_curve filled
+    cur = eng.batt_curve(batch, out, one, want=want)
+    bo = _lib.BattCurveOut(**{k: v.data_ptr() for k, v in cur.items()})
+    co, no = eng.c_outputs(out), _lib.BattNetOpt(0, 0)
+
+    def k1():
+        _lib.check(eng.lib.dgen_batt_curve_net(*args_c, ctypes.byref(co), n, 1, one.data_ptr(), None, ctypes.byref(no),
+                                               ctypes.byref(bo), eng.stream_handle()), "dgen_batt_curve_net")
+    c1 = timed(k1)
+    # dgen_size_with_batt_net alone, on the members dgen_size_with_batt filled
+    a = None if lo is None else eng._to_dev(lo, torch.float64).contiguous()
+    b = None if hi is None else eng._to_dev(hi, torch.float64).contiguous()
+    res = eng.size_with_batt(batch, lo=a, hi=b, want=swant)
+    so = _lib.SwbOut(**{k: v.data_ptr() for k, v in res.items()})
+    opt, sno = _lib.SwbOpt(0.8, 2.0, 0, 0), _lib.SwbNetOpt(0, 0)
+    pa, pb = (None if a is None else a.data_ptr()), (None if b is None else b.data_ptr())
+
+    def fill():
+        _lib.check(eng.lib.dgen_size_with_batt_net(*args_c, n, pa, pb, ctypes.byref(opt), ctypes.byref(sno),
+                                                   ctypes.byref(so), eng.stream_handle()), "dgen_size_with_batt_net")
+    sn = timed(fill)
+    both = timed(lambda: eng.size_with_batt(batch, lo=a, hi=b, want=swant, net=True))
+    first = timed(lambda: eng.size_with_batt(batch, lo=a, hi=b, want=swant))
+    r = eng.size_with_batt(batch, lo=a, hi=b, want=("nfev", "status"), net=True)
+    torch.cuda.synchronize()
+    nfev, st = r["nfev"].cpu().numpy().astype(np.int64), r["status"].cpu().numpy()
+    pad = (-nfev.size) % 64
+    wave_max = np.concatenate([nfev, np.zeros(pad, np.int64)]).reshape(-1, 64).max(axis=1)
+    yard = c1[0] * float(wave_max.mean())
+    fatal = _lib.ST_BOUNDS | _lib.ST_TARIFF | _lib.ST_YEARS | _lib.ST_HOURLY_FORM
+    print(json.dumps({"agents": n, "config": args.config, "wide": args.wide, "net": True,
+                      "max_periods": int(pop.tariffs["P"].max()),
+                      "batt_curve_net_k1_ms": c1[0], "size_with_batt_net_ms": sn[0],
+                      "size_with_batt_both_ms": both[0], "size_with_batt_first_ms": first[0],
+                      "nfev_mean": float(nfev.mean()), "nfev_max": int(nfev.max()),
+                      "wave_max_nfev_mean": float(wave_max.mean()),
+                      "yardstick_ms": yard, "ratio_to_yardstick": sn[0] / yard,
+                      "min_max_ms": {"k1": c1[1:], "net": sn[1:], "both": both[1:], "first": first[1:]},
+                      "agents_flagged": int(((st & fatal) != 0).sum())}))
 
 
 if __name__ == "__main__":
