@@ -210,6 +210,13 @@ class SwbNetOpt(ctypes.Structure):
     _fields_ = [("cap", _i32), ("max_blocks", _i32)]
 
 
+class SwbPeakOpt(ctypes.Structure):
+    """dgen_swb_peak_opt: cap_mixed / cap_kept = the mixed and the kept hours a month's lists hold per agent
+    (<= 0: NB_CAPM, BATT_PEAK_CAPK), max_blocks = the persistent blocks of the launch (<= 0: the blocks resident
+    on the device)."""
+    _fields_ = [("cap_mixed", _i32), ("cap_kept", _i32), ("max_blocks", _i32), ("pad", _i32)]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -229,7 +236,7 @@ EXPORTED = [
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
     "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
-    "dgen_size_with_batt", "dgen_size_with_batt_net",
+    "dgen_size_with_batt", "dgen_size_with_batt_net", "dgen_size_with_batt_peak",
 ]
 
 
@@ -339,6 +346,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_size_with_batt_net.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _i64, _vp, _vp,
                                           ctypes.POINTER(SwbOpt), ctypes.POINTER(SwbNetOpt), ctypes.POINTER(SwbOut),
                                           _vp]
+    L.dgen_size_with_batt_peak.restype = _i32
+    L.dgen_size_with_batt_peak.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _i64, _vp, _vp,
+                                           ctypes.POINTER(SwbOpt), ctypes.POINTER(SwbPeakOpt), ctypes.POINTER(SwbOut),
+                                           _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

@@ -28,10 +28,12 @@ All of the above hold the PV size at kW*.  ``Engine.size_with_batt``
 (dgen_size_with_batt) instead searches the PV size x on the with-battery
 objective, the bank sized from x (x / ratio kWh at hours); net=True (the spec
 key "net_billing": True) adds dgen_size_with_batt_net on the same buffers: the
-agents whose evaluations reach options 2 and 3 are searched too:
+agents whose evaluations reach options 2 and 3 are searched too; peak=True (the
+spec key "peak_billing": True) adds dgen_size_with_batt_peak last: the agents
+whose evaluations reach billed demand charges or kWh/kW tier units:
 
     co_size_spec(spec)                           size_frame's pv_batt_sizing spec as (ratio, hours)
-    co_size_options(spec)                        its net-billing settings (Engine.size_with_batt's keywords)
+    co_size_options(spec)                        its net- and peak-billing settings (Engine.size_with_batt's keywords)
     co_size_summarize(res, npv_ref, status_ref)  the CO_COLUMNS of a search result
     co_size_columns(engine, batch, out, spec)    the per-agent columns of the drop-in switch
                                                  (financial_functions.size_frame(pv_batt_sizing=spec))
@@ -252,16 +254,22 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     return res
 
 
-def co_size_spec(spec) -> Tuple[float, float]:
+PEAK_KEYS = ("peak_billing", "peak_caps", "peak_blocks")
+
+
+def co_size_spec(spec, peak: bool = False) -> Tuple[float, float]:
     """size_frame's pv_batt_sizing spec as (ratio, hours): True for the
     reference's constants (0.8, 2.0), or a dict with "ratio" and / or "hours";
     both must be finite and positive.  The dict's "net_billing", "net_cap" and
-    "net_blocks" keys are not part of the pair (co_size_options(spec))."""
+    "net_blocks" keys are not part of the pair (co_size_options(spec)).  The
+    keys it admits without `peak` are the ones it always admitted; peak=True
+    (what co_size_options and co_size_columns pass) also admits PEAK_KEYS,
+    which are not part of the pair either."""
     if spec is True:
         return REF_PV_TO_BATT, REF_HOURS
     if not isinstance(spec, dict):
         raise ValueError(f"pv_batt_sizing: True or a dict with \"ratio\" / \"hours\" (got {spec!r})")
-    bad = set(spec) - {"ratio", "hours", "net_billing", "net_cap", "net_blocks"}
+    bad = set(spec) - {"ratio", "hours", "net_billing", "net_cap", "net_blocks"} - set(PEAK_KEYS if peak else ())
     if bad:
         raise ValueError(f"pv_batt_sizing: unknown keys {sorted(bad)}")
     r, h = float(spec.get("ratio", REF_PV_TO_BATT)), float(spec.get("hours", REF_HOURS))
@@ -276,8 +284,12 @@ def co_size_options(spec) -> Dict[str, object]:
     it always saw), else {"net": True} with "net_cap" (1 .. _lib.NB_CAPM mixed
     hours a month) and "net_blocks" (>= 1 persistent blocks) where the spec
     names them.  "net_billing" must be a bool, the other two ints (None: the
-    default); they are checked even when net billing is off."""
-    co_size_spec(spec)
+    default); they are checked even when net billing is off.  Likewise
+    "peak_billing": True gives {"peak": True} with "peak_caps" (a pair
+    (cap_mixed, cap_kept) of ints, 1 .. _lib.NB_CAPM and 1 ..
+    _lib.BATT_PEAK_CAPK_MAX, None in either place: the default) and
+    "peak_blocks" (>= 1); neither key implies the other."""
+    co_size_spec(spec, peak=True)
     if spec is True:
         return {}
     net = spec.get("net_billing", False)
@@ -293,7 +305,33 @@ def co_size_options(spec) -> Dict[str, object]:
         if v < 1 or (top is not None and v > top):
             raise ValueError(f"pv_batt_sizing: {key} must be " + (f"1 .. {top}" if top else ">= 1") + f" (got {v})")
         kw[name] = int(v)
-    return {"net": True, **kw} if net else {}
+    peak = spec.get("peak_billing", False)
+    if not isinstance(peak, (bool, np.bool_)):
+        raise ValueError(f"pv_batt_sizing: peak_billing must be a bool (got {peak!r})")
+    pk = {}
+    caps = spec.get("peak_caps")
+    if caps is not None:
+        if not isinstance(caps, (tuple, list)) or len(caps) != 2:
+            raise ValueError(f"pv_batt_sizing: peak_caps must be a pair (cap_mixed, cap_kept) (got {caps!r})")
+        for v, what, top in zip(caps, ("cap_mixed", "cap_kept"), (_lib.NB_CAPM, _lib.BATT_PEAK_CAPK_MAX)):
+            if v is None:
+                continue
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"pv_batt_sizing: peak_caps' {what} must be an int (got {v!r})")
+            if v < 1 or v > top:
+                raise ValueError(f"pv_batt_sizing: peak_caps' {what} must be 1 .. {top} (got {v})")
+        pk["peak_caps"] = tuple(None if v is None else int(v) for v in caps)
+    v = spec.get("peak_blocks")
+    if v is not None:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"pv_batt_sizing: peak_blocks must be an int (got {v!r})")
+        if v < 1:
+            raise ValueError(f"pv_batt_sizing: peak_blocks must be >= 1 (got {v})")
+        pk["peak_blocks"] = int(v)
+    res = {"net": True, **kw} if net else {}
+    if peak:
+        res.update({"peak": True, **pk})
+    return res
 
 
 def co_size_summarize(res: Dict[str, object], npv_ref, status_ref) -> Dict[str, object]:
@@ -323,13 +361,15 @@ def co_size_summarize(res: Dict[str, object], npv_ref, status_ref) -> Dict[str, 
 def co_size_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     """The drop-in switch's per-agent columns (CO_COLUMNS) as host arrays in
     caller order: Engine.size_with_batt of the batch over the sizing call's
-    bracket at co_size_spec(spec), reduced by co_size_summarize() against the
+    bracket at co_size_spec(spec, peak=True), reduced by co_size_summarize() against the
     npv_pv_batt and status of the sized output dict `out`.  float64, except
     pvb_opt_nfev and pvb_opt_status (int64).  Only these [n] vectors cross to
     the host.  With "net_billing": True in the spec the agents on net-billing
-    tariffs are searched too (dgen_size_with_batt_net; co_size_options(spec))."""
+    tariffs are searched too (dgen_size_with_batt_net; co_size_options(spec)), with
+    "peak_billing": True those on billed demand charges and kWh/kW tier units
+    (dgen_size_with_batt_peak)."""
     import torch
-    r, h = co_size_spec(spec)
+    r, h = co_size_spec(spec, peak=True)
     d = engine.size_with_batt(batch, r, h, want=("system_kw", "bank_kwh", "power_kw", "npv", "payback_raw", "nfev",
                                                  "status"), **co_size_options(spec))
     s = co_size_summarize(d, out["npv_pv_batt"], out["status"])

@@ -9142,6 +9142,532 @@ k_size_batt_net(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_
         if (S.nfev) S.nfev[i] = cnt;
     }
 }
+
+// ---------------------------------------------------------------------------
+// The demand-charge and kWh/kW tariffs of that search
+// (dgen_size_with_batt_peak; the definition is in include/dgen_hip.h): the
+// agents whose tariff0, or the tariff of one of their storage rows, is of peak
+// form (kWh/kW tier units, or a billed demand charge) run the same search
+// once more, each evaluation billed under the form of its tariff after the
+// storage switch -- swp_point below for the peak form, swn_point for options
+// 2 and 3 without peaks, swb_point for the bins form.  k_size_batt_net's
+// launch: one lane per candidate, persistent blocks striding over the
+// 64-agent tiles, each with k_batt_curve_peak's workspace slice, a lane's
+// column of it reused by every evaluation and every tile.  swp_point starts
+// each month's mixed and kept counts at 0 and assigns each slot's
+// accumulators and credit banks at month 0, so nothing of an earlier
+// evaluation is read.  swn_point runs on the same slice: its 2 x MAXY
+// per-year doubles fit the (MAXY + 1)(3 + PH) of the peak layout, its list is
+// the mixed list (BnEnt, cap_mixed entries).  LDS is the largest of the three
+// layouts.
+// swp_point is bp_point's body, operation for operation, on (x, ratio, hours)
+// from (tariff0, not switched), the bank and the switch handed in by the
+// caller.  bp_point's ballot for the TS prefetch becomes the lane's own gate
+// (the rates it reads are the same), as in swn_point.
+// ---------------------------------------------------------------------------
+
+// The objective under the peak form: -npv of the dgen_batt_curve_peak point,
+// its members in `a`.  The caller has checked the point's kwh and kw, the
+// tariff's range and periods and its form.  A tariff or record flagged
+// DGEN_ST_DEMAND (the bit is kept), a demand schedule beyond dc_nq or a month
+// beyond a cap leaves NaN members, DGEN_ST_HOURLY_FORM and returns NaN.
+// Not inlined, unlike its two siblings: with all three bodies inlined the
+// kernel measured 5 % slower on C4.
+__device__ __attribute__((noinline)) double swp_point(const dgen_tables& T, const dgen_agents& A, const dgen_cfg& cfg,
+                                                      int64_t i, double* lds, int PH, int dc_nq, double x,
+                                                      const SwnBank& sb, double* accw, BnEnt* ent, int capm,
+                                                      NbEntC* kept, int capk, BcPoint& a) {
+    const double qn = __builtin_nan("");
+    const int tariff = sb.tariff, switched = sb.switched;
+    a = {qn, qn, qn, qn, qn, qn, qn, qn, tariff, switched, DGEN_ST_HOURLY_FORM};
+    const int N = A.econ_life[i];
+    const uint8_t aflags = A.flags[i];
+    const bool is_res = (aflags & 1) != 0;
+    const double kw_star = x;
+    const double bank = sb.bank, otc = sb.otc;
+    double power = sb.power;
+    const dgen_tariff& t = T.tariffs[tariff];
+    const int P = t.P, mo = t.mo;
+    const int info = T.tariffs[A.tariff0[i]].flags | t.flags;
+    // the demand record: its charges when they are billed, its periods' peaks in either case
+    const dgen_demand* const bdem = tariff_demand(T, cfg, t);
+    const dgen_demand* const dem = tariff_demand(T.demand, T.n_demand, true, t);
+    if ((t.flags & DGEN_ST_DEMAND) || (dem && (dem->flags & DGEN_ST_DEMAND))) {
+        a.status |= DGEN_ST_DEMAND;
+        return qn;
+    }
+    const bool netf = net_hourly(t);
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double ls = A.load_kwh[i] / T.shape_sum[lr];
+    const double cs6 = (((kw_star * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    const char* const esch = reinterpret_cast<const char*>(t.wkday);
+    // no record (kWh/kW tiers alone, dc = 0): one period, every hour in it
+    const char* const dsch = dem ? reinterpret_cast<const char*>(dem->wkday) : esch;
+    const uint32_t dmask = dem ? 0xffu : 0u;
+    // TS sell rate (mo 2, not CA, a wholesale row): ts[h] = (double)(float)(wholesale[h] x price_mult)
+    const int wr = (A.wholesale_row && A.price_mult) ? A.wholesale_row[i] : -1;
+    const bool ts_on = mo == 2 && (aflags & 2) == 0 && wr >= 0 && T.wholesale != nullptr;
+    const double* __restrict__ tsp = ts_on ? T.wholesale + (int64_t)wr * NH : T.shape_sum + lr;
+    const int tstride = ts_on ? 1 : 0;
+    const double ts_mult = ts_on ? A.price_mult[i] : 1.0;
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    const double sys_base = 1.0 - (A.pv_deg[i] * 100.0) * 0.01;
+    const double sN = pow_seq(sys_base, N - 1);
+    const double s_lo = sN < 1.0 ? sN : 1.0, s_hi = sN > 1.0 ? sN : 1.0;
+    double* const pl_lb = lds;                                  // lbin
+    double* const pl_al = lds + (size_t)1 * PH * BC_BLOCK;      // SA_L (bins form: lbin again)
+    double* const pl_ag = lds + (size_t)2 * PH * BC_BLOCK;      // SA_g (bins form: gbin)
+    double* const pl_xg = lds + (size_t)3 * PH * BC_BLOCK;      // SX_gw
+    double* const pl_xl = lds + (size_t)4 * PH * BC_BLOCK;      // SX_Lw
+    double* const pl_u = lds + (size_t)5 * PH * BC_BLOCK;       // the year's billed kWh
+    double* const pl_x = lds + (size_t)6 * PH * BC_BLOCK;       // the year's exv (option 4: its generation bins)
+    double* const dq_mx = lds + (size_t)BP_PLANES * PH * BC_BLOCK;      // mxl[q]
+    double* const dq_lb = dq_mx + (size_t)dc_nq * BC_BLOCK;             // lb[q]
+    double* const dq_pk = dq_lb + (size_t)dc_nq * BC_BLOCK;             // the year's peaks
+    double* const acc_e = accw;                                          // [slot]: 0 the no-system year, y = 1 .. N
+    double* const acc_d = accw + (size_t)(MAXY + 1) * BC_BLOCK;
+    double* const acc_c = accw + (size_t)2 * (MAXY + 1) * BC_BLOCK;
+    double* const acc_k = accw + (size_t)BP_ACC * (MAXY + 1) * BC_BLOCK;   // [slot][PH] kWh credit banks (option 0)
+    double soc = cfg.batt_init_soc;
+    bool bad = false;
+    double tq[4] = {0.0, 0.0, 0.0, 0.0}, tn[4] = {0.0, 0.0, 0.0, 0.0};   // TS: this hour quad's rates, the next's
+    if (ts_on) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) tq[j] = tsp[j * tstride];
+    }
+    BmDay cur, nxt;
+    bm_day_load(shp, cfp, esch, dsch, 0, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        for (int p = 0; p < P; p++) {
+            pl_lb[p * BC_BLOCK] = 0.0;
+            pl_al[p * BC_BLOCK] = 0.0;
+            pl_ag[p * BC_BLOCK] = 0.0;
+            pl_xg[p * BC_BLOCK] = 0.0;
+            pl_xl[p * BC_BLOCK] = 0.0;
+        }
+        for (int q = 0; q < dc_nq; q++) {
+            dq_mx[q * BC_BLOCK] = 0.0;
+            dq_lb[q * BC_BLOCK] = 0.0;
+        }
+        int bcur = 0, n_m = 0, dq = 0, n_d = 0;     // the month's lists start empty at every evaluation
+        double b_lb = 0.0, b_al = 0.0, b_ag = 0.0, b_xg = 0.0, b_xl = 0.0, mfloor = 0.0;
+        double d_mx = 0.0, d_lb = 0.0;
+        const int d_end = c_month_start_day[m + 1];
+        for (int d = c_month_start_day[m]; d < d_end; d++) {
+            {   // the next day's rows (December 31 loads itself again)
+                const int dn = d < 364 ? d + 1 : 364;
+                bm_day_load(shp, cfp, esch, dsch, dn, dn < d_end ? m : m + 1, nxt);
+            }
+            double dv[24];
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++)
+                dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+            sort24_desc(dv);
+            const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+            double target = day_target_sorted(dv, power, avail0);
+            {   // dgen_cfg.batt_month_floor: the month's target never falls
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+            const int h0 = d * 24;
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                if ((hh & 3) == 0 && ts_on) {          // the lane's own gate: no wave-wide decision in a search
+                    const int hn = h0 + hh + 4 <= NH - 4 ? h0 + hh + 4 : NH - 4;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) tn[j] = tsp[(hn + j) * tstride];
+                }
+                const float sh = opaque_f(cur.s[hh >> 2][hh & 3]);
+                const double ld = (double)sh * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                const HourStep hs = batt_hour(ld - pv, pv, target, power, bank, soc, cfg, inv_eta_in, in_per_bank,
+                                              out_per_bank);
+                int p = (int)((cur.e[hh >> 3] >> (8 * (hh & 7))) & 0xffu);
+                p = p < P ? p : P - 1;                  // a schedule beyond P: never past the lane's bins
+                if (p != bcur) {
+                    pl_lb[bcur * BC_BLOCK] = b_lb;
+                    pl_al[bcur * BC_BLOCK] = b_al;
+                    pl_ag[bcur * BC_BLOCK] = b_ag;
+                    pl_xg[bcur * BC_BLOCK] = b_xg;
+                    pl_xl[bcur * BC_BLOCK] = b_xl;
+                    bcur = p;
+                    b_lb = pl_lb[p * BC_BLOCK];
+                    b_al = pl_al[p * BC_BLOCK];
+                    b_ag = pl_ag[p * BC_BLOCK];
+                    b_xg = pl_xg[p * BC_BLOCK];
+                    b_xl = pl_xl[p * BC_BLOCK];
+                }
+                int q = (int)((uint32_t)(cur.q[hh >> 3] >> (8 * (hh & 7))) & dmask);
+                if (q >= dc_nq) {                       // a schedule beyond the table's periods: never past the region
+                    bad = true;
+                    q = 0;
+                }
+                if (q != dq) {
+                    dq_mx[dq * BC_BLOCK] = d_mx;
+                    dq_lb[dq * BC_BLOCK] = d_lb;
+                    dq = q;
+                    d_mx = dq_mx[q * BC_BLOCK];
+                    d_lb = dq_lb[q * BC_BLOCK];
+                }
+                const double gk = hs.sys;
+                const double wd = ts_on ? (double)(float)(tq[hh & 3] * ts_mult) : 1.0;
+                const double vlo = ld - gk * s_lo, vhi = ld - gk * s_hi;
+                const double slack = 1e-10 * (fabs(ld) + fabs(gk) * s_hi);
+                // the bins form bills lbin - s gbin: every hour on the import side
+                const bool imp = !netf || fmin(vlo, vhi) > -slack;     // imports (or ~0) at every s
+                const bool exq = !imp && fmax(vlo, vhi) < -slack;      // exports at every s
+                b_lb += ld;
+                b_al += imp ? ld : 0.0;
+                b_ag += imp ? gk : 0.0;
+                b_xg += exq ? gk * wd : 0.0;
+                b_xl += exq ? ld * wd : 0.0;
+                if (!imp && !exq) {
+                    if (n_m < capm) {                   // capm: the mixed entries the workspace holds per lane
+                        BnEnt e;
+                        e.g = gk;
+                        e.sh = sh;
+                        e.hp = ((uint32_t)(h0 + hh) << 8) | (uint32_t)p;
+                        ent[(size_t)n_m * BC_BLOCK] = e;
+                    }
+                    n_m++;
+                }
+                if (fmax(vlo, vhi) > d_lb) {            // may raise some year's peak
+                    if (n_d < capk) {                   // capk: the kept entries the workspace holds per lane
+                        NbEntC e;
+                        e.g = gk;
+                        e.sh = sh;
+                        e.p = q;
+                        kept[(size_t)n_d * BC_BLOCK] = e;
+                    }
+                    n_d++;
+                }
+                d_mx = fmax(d_mx, ld);
+                d_lb = fmax(d_lb, fmin(vlo, vhi));
+                if ((hh & 3) == 3) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) tq[j] = tn[j];
+                }
+            }
+            cur = nxt;
+        }
+        // a list overflowed, or a malformed demand table: the point is not valued
+        if (n_m > capm || n_d > capk || bad) return qn;
+        pl_lb[bcur * BC_BLOCK] = b_lb;
+        pl_al[bcur * BC_BLOCK] = b_al;
+        pl_ag[bcur * BC_BLOCK] = b_ag;
+        pl_xg[bcur * BC_BLOCK] = b_xg;
+        pl_xl[bcur * BC_BLOCK] = b_xl;
+        dq_mx[dq * BC_BLOCK] = d_mx;
+        dq_lb[dq * BC_BLOCK] = d_lb;
+        {   // the kept hours against the month's final lower bounds
+            int w = 0;
+            for (int k = 0; k < n_d; k++) {
+                const NbEntC e = kept[(size_t)k * BC_BLOCK];
+                const double L = (double)e.sh * ls;
+                const double va = L - e.g * s_lo, vb = L - e.g * s_hi;
+                if (fmax(va, vb) > dq_lb[e.p * BC_BLOCK]) {
+                    if (w != k) kept[(size_t)w * BC_BLOCK] = e;
+                    w++;
+                }
+            }
+            n_d = w;
+        }
+        double s_y = 1.0;
+        for (int y = 0; y <= N; y++) {          // the month's bill of slot y: 0 the no-system year
+            const bool gen = y > 0;
+            // ---- the month's peaks: per demand period, and over them ----
+            for (int q = 0; q < dc_nq; q++) dq_pk[q * BC_BLOCK] = gen ? dq_lb[q * BC_BLOCK] : dq_mx[q * BC_BLOCK];
+            if (gen) {
+                for (int k = 0; k < n_d; k++) {
+                    const NbEntC e = kept[(size_t)k * BC_BLOCK];
+                    const double dd = (double)e.sh * ls - e.g * s_y;
+                    const double pk = dq_pk[e.p * BC_BLOCK];
+                    dq_pk[e.p * BC_BLOCK] = dd > pk ? dd : pk;
+                }
+            }
+            double flat = 0.0;
+            for (int q = 0; q < dc_nq; q++) {
+                const double v = dq_pk[q * BC_BLOCK];
+                flat = v > flat ? v : flat;
+            }
+            // ---- the energy side (oracle year_bill, month m) ----
+            double* const cred = acc_k + (size_t)y * PH * BC_BLOCK;
+            double crd = 0.0;
+            if (!netf) {
+                for (int p = 0; p < P; p++) {
+                    const double L = pl_lb[p * BC_BLOCK];
+                    const double G = gen ? s_y * pl_ag[p * BC_BLOCK] : 0.0;
+                    const double net = L - G;
+                    double u;
+                    if (mo == 0) {
+                        double c = m == 0 ? 0.0 : cred[p * BC_BLOCK];
+                        if (net >= 0.0) {
+                            const double use = net < c ? net : c;
+                            u = net - use;
+                            c -= use;
+                        } else {
+                            u = 0.0;
+                            c += -net;
+                        }
+                        cred[p * BC_BLOCK] = c;
+                    } else if (mo == 1) {
+                        u = net > 0.0 ? net : 0.0;
+                        crd += (net < 0.0 ? -net : 0.0) * t.sell[p][0];
+                    } else {
+                        u = L;
+                        crd += G * t.sell[p][0];
+                    }
+                    pl_u[p * BC_BLOCK] = u;
+                }
+            } else {
+                for (int p = 0; p < P; p++) {
+                    pl_u[p * BC_BLOCK] = gen ? pl_al[p * BC_BLOCK] - s_y * pl_ag[p * BC_BLOCK] : pl_lb[p * BC_BLOCK];
+                    pl_x[p * BC_BLOCK] = gen ? s_y * pl_xg[p * BC_BLOCK] - pl_xl[p * BC_BLOCK] : 0.0;
+                }
+                const int n_y = gen ? n_m : 0;
+                for (int k = 0; k < n_y; k++) {     // the mixed hours, in hour order
+                    const BnEnt e = ent[(size_t)k * BC_BLOCK];
+                    const int p = (int)(e.hp & 0xffu);
+                    const double dd = (double)e.sh * ls - s_y * e.g;
+                    if (dd > 0.0) {
+                        pl_u[p * BC_BLOCK] += dd;
+                    } else {
+                        const double wd = ts_on ? (double)(float)(tsp[e.hp >> 8] * ts_mult) : 1.0;
+                        pl_x[p * BC_BLOCK] += (-dd) * wd;
+                    }
+                }
+                if (gen) {
+                    if (ts_on) {
+                        for (int p = 0; p < P; p++) crd += pl_x[p * BC_BLOCK];
+                    } else {
+                        for (int p = 0; p < P; p++) crd += pl_x[p * BC_BLOCK] * t.sell[p][0];
+                    }
+                }
+            }
+            double U = 0.0;
+            for (int p = 0; p < P; p++) U += pl_u[p * BC_BLOCK];
+            const double charge = bp_energy_charge(t, m, pl_u, U, flat);
+            double bill = t.fixed;
+            double carry = m == 0 ? 0.0 : acc_c[(size_t)y * BC_BLOCK];
+            if (mo == 0) {
+                bill += charge;
+                if (m == 11) {
+                    double c = 0.0;
+                    for (int p = 0; p < P; p++) c += cred[p * BC_BLOCK];
+                    bill -= c * cfg.nm_yearend_sell_rate;
+                }
+            } else if (mo == 1 || mo == 3) {
+                const double e = charge - crd - carry;
+                carry = e < 0.0 ? -e : 0.0;
+                bill += e < 0.0 ? 0.0 : e;
+            } else if (mo == 4) {
+                bill += charge - crd;
+            } else {
+                bill += charge;
+                bill -= crd;
+            }
+            // ---- the month's demand charge (oracle year_demand): the flat tiers, then the periods ----
+            double dch = 0.0;
+            if (bdem) {
+                dch = dc_tier_charge(flat, bdem->flat_cap[m], bdem->flat_price[m], bdem->flat_nt[m]);
+                for (int q = 0; q < dc_nq; q++)
+                    dch += dc_tier_charge(dq_pk[q * BC_BLOCK], bdem->tou_cap[q], bdem->tou_price[q], bdem->tou_nt[q]);
+            }
+            acc_c[(size_t)y * BC_BLOCK] = carry;
+            acc_e[(size_t)y * BC_BLOCK] = (m == 0 ? 0.0 : acc_e[(size_t)y * BC_BLOCK]) + bill;
+            acc_d[(size_t)y * BC_BLOCK] = (m == 0 ? 0.0 : acc_d[(size_t)y * BC_BLOCK]) + dch;
+            if (gen) s_y = s_y * sys_base;
+        }
+    }
+    // ---- the Cashloan (orc_cashloan) over the stored years, as k_batt_curve steps it ----
+    const double rate_base = 1.0 + (A.inflation[i] * 100.0) * 0.01 + (A.escalator[i] * 100.0) * 0.01;
+    const double vor = A.vor[i];
+    const double system_costs = (kw_star > 0.0) ? A.capex_combined[i] * kw_star : A.capex[i] * kw_star;
+    const double batt_costs = A.batt_capex_kwh[i] * bank * 0.7;
+    const double C = ((system_costs + batt_costs) * A.ccm[i]) + 0.0 + otc;
+    const int market = is_res ? 0 : 1, depr_type = is_res ? 0 : 2;
+    const double infl = (A.inflation[i] * 100.0) * 0.01;
+    const double real = (A.real_discount[i] * 100.0) * 0.01;
+    const double nom = (1.0 + real) * (1.0 + infl) - 1.0;
+    const double fed = ((A.tax_rate[i] * 100.0) * 0.7) * 0.01, sta = ((A.tax_rate[i] * 100.0) * 0.3) * 0.01;
+    const double debt = (100.0 - (A.down_payment[i] * 100.0)) * 0.01 * C;
+    const double r = cfg.loan_rate_pct * 0.01;
+    const int term = A.loan_term[i];
+    double pmt = 0.0;
+    if (term > 0 && debt != 0.0) {
+        if (r != 0.0) {
+            const double f = pow_seq(1.0 + r, term);
+            pmt = debt * r / (1.0 - 1.0 / f);
+        } else {
+            pmt = debt / (double)term;
+        }
+    }
+    double itc = A.itc_frac[i] * 0.01 * C;
+    if (itc > cfg.itc_fed_max) itc = cfg.itc_fed_max;
+    const double basis = C - 0.5 * itc;
+    const double ins = cfg.insurance_rate_pct * 0.01 * C;
+    const double rr = 1.0 / (1.0 + nom);
+    // the year's demand total joins its energy total once (orc_ur5)
+    const double wo_base = bdem ? acc_e[0] + acc_d[0] : acc_e[0];
+    a.w1 = 0.0;
+    a.wo1 = 0.0;
+    a.life = 0.0;
+    double balance = debt, acc = 0.0, df = rr, cum = -C, pb = 1e99;
+    bool paid = false;
+    double r_y = 1.0, o_y = 1.0;                  // pow_seq's running products
+    for (int y = 1; y <= N; y++) {
+        const double wb = bdem ? acc_e[(size_t)y * BC_BLOCK] + acc_d[(size_t)y * BC_BLOCK] : acc_e[(size_t)y * BC_BLOCK];
+        const double w = wb * r_y;
+        const double wo = wo_base * r_y;
+        const double ev = (wo - w) + vor;           // ff:275
+        if (y == 1) {
+            a.w1 = w;
+            a.wo1 = wo;
+        }
+        a.life += ev;
+        const double oe = ins * o_y;
+        double interest = 0.0, payment = 0.0;
+        if (y <= term && pmt != 0.0) {
+            interest = balance * r;
+            payment = pmt;
+            balance = balance - (pmt - interest);
+        }
+        const double itc_y = (y == 1) ? itc : 0.0;
+        double sta_tax = 0.0, fed_tax = 0.0;
+        if (market != 0) {
+            const double dep = depr_frac(depr_type, y, cfg.depr_sl_years) * basis;
+            sta_tax = sta * (ev - oe - interest - dep);
+            fed_tax = fed * (ev - oe - interest - dep - sta_tax);
+        }
+        const double taxsav = itc_y - sta_tax - fed_tax;
+        const double atcf = ev - oe - payment + taxsav;
+        const double cfp = ev - oe + taxsav;
+        acc += atcf * df;
+        df *= rr;
+        cum += cfp;
+        if (!paid && cum > 0.0) {
+            pb = (cfp != 0.0) ? (double)y - cum / cfp : (double)y - 0.5;
+            paid = true;
+        }
+        r_y = r_y * rate_base;
+        o_y = o_y * (1.0 + infl);
+    }
+    a.npv = -(C - debt) + acc;
+    a.payback = pb;
+    a.cost = C;
+    a.bank = bank;
+    a.power = power;
+    a.status = info & (DGEN_ST_EMPTY_EC | DGEN_ST_DEMAND);
+    return -a.npv;
+}
+
+__device__ __forceinline__ bool peak_form(const dgen_tables& T, const dgen_cfg& cfg, const dgen_tariff& t) {
+    return peak_unit(t) || tariff_demand(T, cfg, t) != nullptr;
+}
+
+__global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_size_batt_peak(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, const double* __restrict__ lo_p,
+                 const double* __restrict__ hi_p, double ratio, double hours, int trace_n, dgen_swb_out S,
+                 char* __restrict__ ws, int capm, int capk, int dc_nq) {
+    const int PH = lds_half(T.max_periods);
+    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BC_BLOCK]
+    char* const wsb = ws + (size_t)blockIdx.x * bp_block_bytes(PH, capm, capk);
+    double* const accw = reinterpret_cast<double*>(wsb) + threadIdx.x;
+    BnEnt* const ent = reinterpret_cast<BnEnt*>(wsb + bp_acc_bytes(PH)) + threadIdx.x;
+    NbEntC* const kept = reinterpret_cast<NbEntC*>(wsb + bp_acc_bytes(PH) + (size_t)capm * BC_BLOCK * sizeof(BnEnt)) +
+                         threadIdx.x;
+    const double q = __builtin_nan("");
+    const int64_t step = (int64_t)gridDim.x * BC_BLOCK;
+    for (int64_t i = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; i < n; i += step) {
+        // ---- the candidate rule: from the tables, cfg and the agent's columns alone ----
+        const int t0 = A.tariff0[i];
+        const int N = A.econ_life[i];
+        if (N < 1 || N > MAXY) continue;
+        if (t0 < 0 || t0 >= T.n_tariffs) continue;
+        if (T.tariffs[t0].flags & DGEN_ST_UNIT) continue;
+        double low, high;
+        if (lo_p) {
+            low = lo_p[i];
+            high = hi_p[i];
+        } else {                                                         // k_size_batt's bracket (ff:440-444)
+            const double max_load = A.load_kwh[i] / T.cf_naep[A.cf_row[i]];
+            low = max_load * 0.8;
+            high = max_load * 1.25;
+        }
+        if (!isfinite(low) || !isfinite(high) || !(low > 0.0) || !(low < high)) continue;
+        bool pkf = peak_form(T, cfg, T.tariffs[t0]);
+        {
+            const dgen_switch* rows = T.switches + A.sw_storage_off[i];
+            const int rc = A.sw_storage_cnt[i];
+            for (int r = 0; r < rc && !pkf; r++) {
+                const int tt = rows[r].tariff;
+                if (tt >= 0 && tt < T.n_tariffs) pkf = peak_form(T, cfg, T.tariffs[tt]);
+            }
+        }
+        if (!pkf) continue;                     // no evaluation of this agent can be of peak form
+        // ---- the search, as k_size_batt runs it ----
+        const double span = high - low;
+        const double tl = (span > 1.0 ? span : 1.0) * 1e-3;
+        const double fl_tl = floor(tl);
+        const double xatol = fl_tl < 2.0 ? 2.0 : fl_tl;
+        const int status = A.load_kwh[i] == 0.0 ? DGEN_ST_ZERO_LOAD : 0;
+        double* const tx = (trace_n > 0 && S.trace_x) ? S.trace_x + i * trace_n : nullptr;
+        double* const tf = (trace_n > 0 && S.trace_f) ? S.trace_f + i * trace_n : nullptr;
+        for (int k = 0; k < trace_n; k++) {
+            if (tx) tx[k] = q;
+            if (tf) tf[k] = q;
+        }
+        if (S.system_kw) S.system_kw[i] = q;
+        int cnt = 0;
+        bool dead = false;
+        double best = 0.0;
+        int nfev = 0;
+        double x_last = 0.0;
+        const double kw = brent_bounded(
+            [&](double x) __attribute__((always_inline)) {
+                if (dead) return q;
+                BcPoint a;
+                double f;
+                const SwnBank sb = swn_bank(T, A, cfg, i, batt_on, x, ratio, hours);
+                const double kwh = x / ratio, kwp = kwh / hours;
+                // 0: swb_point (the bins form valued, the rest flagged by its rules), 1: options 2 and 3, 2: peaks
+                int form = 0;
+                if (kwh >= 0.0 && !isinf(kwh) && (!(kwh > 0.0) || (kwp > 0.0 && !isinf(kwp))) && sb.tariff >= 0 &&
+                    sb.tariff < T.n_tariffs) {
+                    const dgen_tariff& t = T.tariffs[sb.tariff];
+                    if (t.P >= 1 && t.P <= PH && t.T >= 1 && t.T <= MAXT)
+                        form = peak_form(T, cfg, t) ? 2 : net_hourly(t) ? 1 : 0;
+                }
+                if (form == 2) f = swp_point(T, A, cfg, i, lds, PH, dc_nq, x, sb, accw, ent, capm, kept, capk, a);
+                else if (form == 1) f = swn_point(T, A, cfg, i, lds, PH, x, sb, accw, ent, capm, a);
+                else f = swb_point(T, A, cfg, i, batt_on, lds, PH, x, ratio, hours, a);
+                if (cnt < trace_n) {
+                    if (tx) tx[cnt] = x;
+                    if (tf) tf[cnt] = f;
+                }
+                dead = (a.status & SWB_FATAL) != 0;
+                if (a.status & DGEN_ST_TARIFF) a.status |= DGEN_ST_HOURLY_FORM;   // every form that ends the agent
+                if (dead || cnt == 0 || f <= best) {
+                    best = f;
+                    a.status |= status;
+                    swb_store(S, i, a);
+                }
+                cnt += 1;
+                return f;
+            },
+            low, high, xatol, &nfev, &x_last);
+        if (S.system_kw && !dead) S.system_kw[i] = kw;
+        if (S.nfev) S.nfev[i] = cnt;
+    }
+}
 #endif  // !DGEN_TU_SEARCH
 
 }  // namespace
@@ -11098,6 +11624,108 @@ int32_t dgen_size_with_batt_net(dgen_ctx* c, const dgen_tables* T, const dgen_ag
     }
     hipLaunchKernelGGL(k_size_batt_net, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A,
                        c->cfg, n, c->battery, lo, hi, ratio, hours, trace_n, *out, c->bn_ws, cap);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_size_with_batt_peak(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, int64_t n, const double* lo,
+                                 const double* hi, const dgen_swb_opt* opt, const dgen_swb_peak_opt* popt,
+                                 const dgen_swb_out* out, void* stream) {
+    if (!c || !T || !A || !out || n < 0) {
+        set_err("dgen_size_with_batt_peak: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (!out->status) {
+        set_err("dgen_size_with_batt_peak: out->status is NULL");
+        return DGEN_E_ARG;
+    }
+    if ((lo == nullptr) != (hi == nullptr)) {
+        set_err("dgen_size_with_batt_peak: lo and hi must both be given or both be NULL");
+        return DGEN_E_ARG;
+    }
+    double ratio = 0.8, hours = 2.0;
+    int trace_n = 0;
+    if (opt) {
+        if (opt->pv_to_batt_ratio > 0.0) ratio = opt->pv_to_batt_ratio;
+        if (opt->hours > 0.0) hours = opt->hours;
+        trace_n = opt->trace_n;
+    }
+    if (trace_n < 0 || trace_n > DGEN_SWB_TRACE_MAX) {
+        set_err("dgen_size_with_batt_peak: trace_n = %d, must be 0 .. %d", trace_n, DGEN_SWB_TRACE_MAX);
+        return DGEN_E_ARG;
+    }
+    const int capm = (popt && popt->cap_mixed > 0) ? popt->cap_mixed : DGEN_NB_CAPM;
+    const int capk = (popt && popt->cap_kept > 0) ? popt->cap_kept : DGEN_BATT_PEAK_CAPK;
+    if (capm > DGEN_NB_CAPM || capk > BP_CAPK_MAX) {
+        set_err("dgen_size_with_batt_peak: cap_mixed = %d, cap_kept = %d hours per month, at most %d and %d", capm,
+                capk, DGEN_NB_CAPM, BP_CAPK_MAX);
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->cf_naep || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand) || (T->n_switches > 0 && !T->switches)) {
+        set_err("dgen_size_with_batt_peak: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    const void* cols[] = {A->load_row, A->cf_row, A->load_kwh, A->flags, A->tariff0, A->sw_storage_off,
+                          A->sw_storage_cnt, A->econ_life, A->loan_term, A->inflation, A->pv_deg, A->escalator,
+                          A->down_payment, A->tax_rate, A->real_discount, A->itc_frac, A->capex, A->capex_combined,
+                          A->batt_capex_kwh, A->ccm, A->vor};
+    for (const void* p : cols)
+        if (!p) { set_err("dgen_size_with_batt_peak: missing agent column"); return DGEN_E_ARG; }
+    if (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1) {
+        set_err("dgen_size_with_batt_peak: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not replayed: the daily plan under constant efficiencies only");
+        return DGEN_E_ARG;
+    }
+    const int64_t tiles = (n + BC_BLOCK - 1) / BC_BLOCK;
+    if (tiles > 0x7fffffff) {
+        set_err("dgen_size_with_batt_peak: n = %lld exceeds the launch grid", (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    // the largest of the three forms' layouts: swb_point's 26 planes cover swn_point's 7, swp_point adds
+    // its demand periods to those 7
+    const int PH = lds_half(T->max_periods);
+    const int dc_nq = (T->max_dc_periods > 0 && T->max_dc_periods <= DCP) ? T->max_dc_periods : DCP;
+    const size_t lds_bins = (size_t)BC_PLANES * PH * BC_BLOCK * sizeof(double);
+    const size_t lds = lds_bins > bp_lds_bytes(PH, dc_nq) ? lds_bins : bp_lds_bytes(PH, dc_nq);
+    HIP_TRY(hipSetDevice(c->device));
+    if (lds > (size_t)c->lds_max) {
+        set_err("dgen_size_with_batt_peak: %zu B of LDS for %d periods and %d demand periods exceed the device's %d B "
+                "per block", lds, PH, dc_nq, c->lds_max);
+        return DGEN_E_ARG;
+    }
+    if (lds > 65536)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_size_batt_peak),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // persistent blocks: as many as the device holds at once (or popt->max_blocks), each with its own
+    // workspace slice, striding over the 64-agent tiles
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_size_batt_peak),
+                                                     BC_BLOCK, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        per_cu = 0;
+    }
+    per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
+    int64_t blocks = (int64_t)per_cu * c->n_cu;
+    if (popt && popt->max_blocks > 0 && popt->max_blocks < blocks) blocks = popt->max_blocks;
+    if (tiles < blocks) blocks = tiles;
+    const size_t need = (size_t)blocks * bp_block_bytes(PH, capm, capk);
+    if (need > c->bp_ws_cap) {
+        if (c->bp_ws) HIP_TRY(hipFree(c->bp_ws));       // waits for the kernels that read it
+        c->bp_ws = nullptr;
+        c->bp_ws_cap = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&c->bp_ws), need) != hipSuccess) {
+            (void)hipGetLastError();
+            c->bp_ws = nullptr;
+            set_err("dgen_size_with_batt_peak: %zu B of workspace for %lld blocks of %d mixed and %d kept hours", need,
+                    (long long)blocks, capm, capk);
+            return DGEN_E_HIP;
+        }
+        c->bp_ws_cap = need;
+    }
+    hipLaunchKernelGGL(k_size_batt_peak, dim3((unsigned)blocks), dim3(BC_BLOCK), lds, (hipStream_t)stream, *T, *A,
+                       c->cfg, n, c->battery, lo, hi, ratio, hours, trace_n, *out, c->bp_ws, capm, capk, dc_nq);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

@@ -843,7 +843,8 @@ class Engine:
 
     def size_with_batt(self, batch: AgentBatch, ratio: float = 0.8, hours: float = 2.0, lo=None, hi=None,
                        trace: int = 0, want=None, net: bool = False, net_cap: Optional[int] = None,
-                       net_blocks: Optional[int] = None) -> Dict[str, object]:
+                       net_blocks: Optional[int] = None, peak: bool = False, peak_caps=None,
+                       peak_blocks: Optional[int] = None) -> Dict[str, object]:
         """PV size of `batch` on the with-battery objective --
         dgen_size_with_batt, async on the current stream: the sizing call's
         bounded search over the PV size x, minimising -npv of the PV+battery
@@ -867,7 +868,14 @@ class Engine:
         agent (default _lib.NB_CAPM; an evaluation beyond it ends the agent
         flagged); net_blocks: a cap on the launch's persistent blocks and so
         on its workspace (default: the blocks resident on the device; results
-        do not depend on it).  The definitions are in include/dgen_hip.h."""
+        do not depend on it).  peak=True issues dgen_size_with_batt_peak last,
+        on the same buffers and stream: the agents whose tariff0 or storage
+        rows reach a billed demand charge or kWh/kW tier units are searched
+        with those evaluations billed from the month's peaks; it implies
+        nothing about net.  peak_caps: (cap_mixed, cap_kept), the mixed and
+        the kept hours a month may hold per agent (None, or None in either
+        place: _lib.NB_CAPM, _lib.BATT_PEAK_CAPK); peak_blocks: as net_blocks.
+        The definitions are in include/dgen_hip.h."""
         torch = _torch()
         want = tuple(_lib.SWB_FIELDS if want is None else want)
         bad = [k for k in want if k not in _lib.SWB_FIELDS]
@@ -903,6 +911,14 @@ class Engine:
                                                         ctypes.byref(batch.c_agents), n, _ptr(a), _ptr(b),
                                                         ctypes.byref(opt), ctypes.byref(no), ctypes.byref(so),
                                                         self.stream_handle()), "dgen_size_with_batt_net")
+        if peak:
+            capm, capk = (None, None) if peak_caps is None else peak_caps
+            po = _lib.SwbPeakOpt(0 if capm is None else int(capm), 0 if capk is None else int(capk),
+                                 0 if peak_blocks is None else int(peak_blocks), 0)
+            _lib.check(self.lib.dgen_size_with_batt_peak(self.ctx, ctypes.byref(self.tables),
+                                                         ctypes.byref(batch.c_agents), n, _ptr(a), _ptr(b),
+                                                         ctypes.byref(opt), ctypes.byref(po), ctypes.byref(so),
+                                                         self.stream_handle()), "dgen_size_with_batt_peak")
         self._keep["_swb"] = (a, b)           # alive until the next call (stream order)
         return res
 

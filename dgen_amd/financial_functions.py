@@ -670,7 +670,9 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     "net_billing": True also searches the agents whose tariff bills hourly
     imports (metering options 2 and 3: every CA agent and the net-billing
     tariffs; dgen_size_with_batt_net), with "net_cap" and "net_blocks" that
-    entry's options (batt_sizing.co_size_options).  No plane is read: the
+    entry's options, and "peak_billing": True those on billed demand charges
+    or kWh/kW tier units (dgen_size_with_batt_peak, issued last), with
+    "peak_caps" and "peak_blocks" (batt_sizing.co_size_options).  No plane is read: the
     same bits in every hourly mode and sub-batching.  None (the default) leaves
     the frame unchanged."""
     import time

@@ -72,7 +72,7 @@ extern "C" {
                                    /* the point's tariff bills hourly imports, demand  */
                                    /* charges or kWh/kW tiers, which they do not cover. */
                                    /* After the _net / _peak fill-ins of the curve, or  */
-                                   /* dgen_size_with_batt_net: see those entries' text  */
+                                   /* dgen_size_with_batt_net / _peak: see their text   */
 
 /* Engine configuration: the PySAM config defaults the reference never sets
  * (CustomGenerationBattery{Residential,Commercial}, ff:59-80) plus the
@@ -1301,6 +1301,88 @@ typedef struct { int32_t cap; int32_t max_blocks; } dgen_swb_net_opt;   /* NULL 
 int32_t dgen_size_with_batt_net(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents, int64_t n,
                                 const double* lo, const double* hi, const dgen_swb_opt* opt,
                                 const dgen_swb_net_opt* nopt, const dgen_swb_out* out, void* stream);
+
+/* The demand-charge and kWh/kW tariffs of that search (additive to ABI 14):
+ * the agents the two entries above end with DGEN_ST_HOURLY_FORM because an
+ * evaluation's tariff is of peak form -- kWh/kW tier units (codes 1, 3), or a
+ * demand charge that is billed (cfg.skip_demand_charges == 0 and the tariff's
+ * dc names a record in 1 .. n_demand), under any metering option.  The entry
+ * fills in with dgen_size_with_batt_net's contract: same lo, hi, opt, out
+ * buffers and stream, its candidates written in full and nothing else.
+ * Call it LAST: after dgen_size_with_batt, and after dgen_size_with_batt_net
+ * where that one is used.  Unlike the what-if fill-ins the order matters: an
+ * agent may be a candidate of both fill-ins (a net-billing tariff0 with a
+ * storage row onto a demand tariff); the net entry ends it at its first
+ * peak-form evaluation, this entry values it, and the last writer's bits stay.
+ * Candidates are decided from the tables, cfg and the agent columns alone (out
+ * is not read).  Agent i is a candidate when all of these hold:
+ *   - its bracket (lo, hi, or the default bracket when both are NULL) is valid
+ *     under dgen_size_with_batt's rules, bit for bit;
+ *   - its economic life is in 1 .. DGEN_MAXY;
+ *   - tariff0[i] is inside the table and does not carry DGEN_ST_UNIT;
+ *   - tariff0[i], or the tariff of at least one of its sw_storage rows whose
+ *     index is inside the table, is of peak form.
+ * Every other agent is not written at all: no member, no status, no trace row
+ * (a batch without such tariffs leaves at that check).
+ * A candidate runs dgen_size_with_batt's search: the same bounded minimiser,
+ * xatol by ff:444, every evaluation from (tariff0, not switched), ratio, hours
+ * and trace_n from opt.  f(x) = -npv takes the form of the tariff after the
+ * storage rate switch on that evaluation's bank:
+ *   peak form (any metering option):
+ *       the dgen_batt_curve_peak point at popt->cap_mixed / popt->cap_kept,
+ *       bit for bit;
+ *   options 2 or 3 without peaks:
+ *       the dgen_batt_curve_net point at cap = popt->cap_mixed, bit for bit;
+ *   bins form:
+ *       the dgen_batt_curve point, bit for bit,
+ * each with sized.system_kw = x, sized.tariff_final = tariff0,
+ * sized.switched = 0, sized.status = 0, kwh = x / ratio, kw_pts = kwh / hours.
+ * One search may cross all three forms; a candidate whose evaluations never
+ * met the peak form gets the bits the earlier calls wrote, or would have
+ * written.
+ * An evaluation ends the agent when its tariff after the switch is outside the
+ * table or beyond tables->max_periods (this one adds DGEN_ST_TARIFF), when the
+ * tariff or its demand record carries DGEN_ST_DEMAND (the bit stays in the
+ * status), when its demand schedule names a period at or beyond
+ * tables->max_dc_periods, or when a month holds more than cap_mixed mixed or
+ * cap_kept kept hours.  dgen_size_with_batt's rule for such a lane holds: NaN
+ * in every double member, DGEN_ST_HOURLY_FORM, tariff and switched of that
+ * evaluation, nfev up to and including it; no later request walks the year.
+ * Nothing is stored past a cap.
+ * Every candidate is written in full by dgen_size_with_batt's rule (the
+ * members of the evaluation at system_kw, nfev, the trace rows NaN beyond
+ * nfev, DGEN_ST_ZERO_LOAD and the DGEN_ST_EMPTY_EC / _DEMAND flags of tariff0
+ * and of the tariff billed at system_kw).  NULL members are not written;
+ * status must be given.
+ * popt->cap_mixed: 1 .. DGEN_NB_CAPM, popt->cap_kept: 1 ..
+ * DGEN_BATT_PEAK_CAPK_MAX (NULL or <= 0: DGEN_NB_CAPM and
+ * DGEN_BATT_PEAK_CAPK; above the maximum: DGEN_E_ARG).  popt->max_blocks: a
+ * positive value caps the persistent blocks of the launch and so the
+ * workspace; NULL or <= 0: the blocks resident on the device.  Results do not
+ * depend on it.  The lists live in dgen_batt_curve_peak's ctx-owned workspace,
+ * sized by the blocks, not by n (per block (DGEN_MAXY + 1) x (3 +
+ * max_periods) x 512 B of per-year state, cap_mixed x 1024 B and cap_kept x
+ * 1024 B of entries), grown on demand and freed by dgen_close; calls on one
+ * ctx must be stream-ordered.  The net-billing evaluations use the same slice.
+ * One lane per candidate walks the year once per evaluation; every evaluation
+ * starts its lists and accumulators afresh.  Agent i's results do not depend
+ * on n, on its neighbours or on the blocks; no atomics, no cross-lane traffic:
+ * run-to-run identical.  The kernel keeps the largest of the three forms'
+ * layouts, max(26 x max_periods, 7 x max_periods + 3 x max_dc_periods) x
+ * 512 B of LDS per 64 agents.
+ * Argument errors are dgen_size_with_batt's (trace_n out of range, one of
+ * lo / hi NULL, out->status NULL, batt_update_hours == 1 or
+ * batt_loss_model == 1: DGEN_E_ARG); after dgen_set_battery(ctx, 0) every bank
+ * is 0 and the search bills the PV-only peaks.
+ * After the three calls DGEN_ST_HOURLY_FORM means: tariff0 carries
+ * DGEN_ST_UNIT, an evaluation met a tariff or demand record flagged
+ * DGEN_ST_DEMAND or a demand schedule beyond max_dc_periods, or a month's list
+ * overflowed its cap.                                                         */
+typedef struct { int32_t cap_mixed; int32_t cap_kept; int32_t max_blocks; int32_t pad; } dgen_swb_peak_opt;  /* NULL or <= 0: the defaults */
+
+int32_t dgen_size_with_batt_peak(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents, int64_t n,
+                                 const double* lo, const double* hi, const dgen_swb_opt* opt,
+                                 const dgen_swb_peak_opt* popt, const dgen_swb_out* out, void* stream);
 
 #ifdef __cplusplus
 }
