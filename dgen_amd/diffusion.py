@@ -106,35 +106,46 @@ def _dev(engine, a, dtype):
     return engine._to_dev(np.asarray(a), dtype)
 
 
+def max_market_share_arrays(engine, payback, row, tab, fmin: int, min_pb: float, max_pb: float
+                            ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Run k_max_market_share on host columns: payback [n] float64 and the
+    agents' curve rows [n] int32 (-1: no curve) against mms_table()'s dense
+    table -> (payback_period_bounded float64, payback_period_as_factor int64,
+    max_market_share float64)."""
+    import torch
+    L = _bind(engine.lib)
+    tab = np.asarray(tab, dtype=np.float64)
+    n = len(payback)
+    t_tab = _dev(engine, tab, torch.float64)
+    t_pb, t_row = _dev(engine, payback, torch.float64), _dev(engine, row, torch.int32)
+    b = torch.empty(n, dtype=torch.float64, device=engine.dev)
+    fct = torch.empty(n, dtype=torch.int64, device=engine.dev)
+    mms = torch.empty(n, dtype=torch.float64, device=engine.dev)
+    tb = MmsTable(mms=t_tab.data_ptr(), n_rows=tab.shape[0], n_factors=tab.shape[1],
+                  factor_min=fmin, pad=0, min_pb=min_pb, max_pb=max_pb)
+    _lib.check(L.dgen_max_market_share(engine.ctx, ctypes.byref(tb), t_pb.data_ptr(), t_row.data_ptr(),
+                                       n, b.data_ptr(), fct.data_ptr(), mms.data_ptr(),
+                                       engine.stream_handle()), "dgen_max_market_share")
+    torch.cuda.synchronize(engine.dev)
+    return b.cpu().numpy(), fct.cpu().numpy(), mms.cpu().numpy()
+
+
 def calc_max_market_share(dataframe: pd.DataFrame, max_market_share_df: pd.DataFrame,
                           engine=None) -> pd.DataFrame:
     """ff:1264 -- attach max_market_share by (sector_abbr, payback factor)."""
-    import torch
     from .financial_functions import get_engine
     eng = engine or get_engine()
-    L = _bind(eng.lib)
     in_cols = list(dataframe.columns)
     df = dataframe.reset_index()
     df['business_model'] = 'host_owned'
     df['metric'] = 'payback_period'
     tab, rows, fmin, min_pb, max_pb = mms_table(max_market_share_df)
-    n = len(df)
     row = np.array([rows.get(s, -1) for s in df['sector_abbr']], dtype=np.int32)
     pb = df['payback_period'].to_numpy(dtype=np.float64)
-    t_tab = _dev(eng, tab, torch.float64)
-    t_pb, t_row = _dev(eng, pb, torch.float64), _dev(eng, row, torch.int32)
-    b = torch.empty(n, dtype=torch.float64, device=eng.dev)
-    fct = torch.empty(n, dtype=torch.int64, device=eng.dev)
-    mms = torch.empty(n, dtype=torch.float64, device=eng.dev)
-    tb = MmsTable(mms=t_tab.data_ptr(), n_rows=tab.shape[0], n_factors=tab.shape[1],
-                  factor_min=fmin, pad=0, min_pb=min_pb, max_pb=max_pb)
-    _lib.check(L.dgen_max_market_share(eng.ctx, ctypes.byref(tb), t_pb.data_ptr(), t_row.data_ptr(),
-                                       n, b.data_ptr(), fct.data_ptr(), mms.data_ptr(),
-                                       eng.stream_handle()), "dgen_max_market_share")
-    torch.cuda.synchronize(eng.dev)
-    df['payback_period_bounded'] = b.cpu().numpy()
-    df['payback_period_as_factor'] = pd.array(fct.cpu().numpy(), dtype='Int64')
-    df['max_market_share'] = mms.cpu().numpy()
+    b, fct, mms = max_market_share_arrays(eng, pb, row, tab, fmin, min_pb, max_pb)
+    df['payback_period_bounded'] = b
+    df['payback_period_as_factor'] = pd.array(fct, dtype='Int64')
+    df['max_market_share'] = mms
     return df[in_cols + ['max_market_share', 'metric']]
 
 

@@ -52,7 +52,9 @@ def initial_market_shares(state, sector, tech, weight, capex, caps: Dict) -> Dic
         for i in rows:
             w = weight[i]
             with np.errstate(all="ignore"):
-                portion = w / dev if dev > 0 else 1.0 / cnt
+                # numpy division: a group with no countable weight has
+                # agent_count 0 and pandas gives 1 / 0 = inf, not an exception
+                portion = w / dev if dev > 0 else np.float64(1.0) / np.float64(cnt)
                 adopt = portion * pv_n
                 skc = (portion * sys_mw) * 1000.
                 bkw = (portion * batt_mw) * 1000.0
