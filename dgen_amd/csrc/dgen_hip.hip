@@ -7262,7 +7262,13 @@ struct BcPoint {
     double npv, payback, cost, bank, power, w1, wo1, life;
     int tariff, switched, status;
 };
-__device__ __forceinline__ void bc_store(const dgen_batt_curve_out& S, int64_t o, const BcPoint& a) {
+__device__ __forceinline__ BcPoint bc_nan_point(int tariff, int switched, int status) {
+    const double q = __builtin_nan("");
+    return {q, q, q, q, q, q, q, q, tariff, switched, status};
+}
+// S: dgen_batt_curve_out at o = k n + i, or dgen_swb_out at i, whose status column is required (status_always)
+template <class Out>
+__device__ __forceinline__ void bc_store(const Out& S, int64_t o, const BcPoint& a, bool status_always = false) {
     if (S.npv) S.npv[o] = a.npv;
     if (S.payback_raw) S.payback_raw[o] = a.payback;
     if (S.total_cost) S.total_cost[o] = a.cost;
@@ -7273,14 +7279,13 @@ __device__ __forceinline__ void bc_store(const dgen_batt_curve_out& S, int64_t o
     if (S.lifetime_savings) S.lifetime_savings[o] = a.life;
     if (S.tariff) S.tariff[o] = a.tariff;
     if (S.switched) S.switched[o] = a.switched;
-    if (S.status) S.status[o] = a.status;
+    if (status_always || S.status) S.status[o] = a.status;
 }
 __device__ __forceinline__ void bc_flag(const dgen_batt_curve_out& S, int64_t o, int tariff, int switched,
                                         int status) {
-    const double q = __builtin_nan("");
-    const BcPoint z = {q, q, q, q, q, q, q, q, tariff, switched, status};
-    bc_store(S, o, z);
+    bc_store(S, o, bc_nan_point(tariff, switched, status));
 }
+
 
 // oracle year_bill (options 0, 1, 4) from the lane's (month, period) bins at
 // net = L - s G; gen false: the no-system year (G = 0).  lds: the lane's column.
@@ -8443,20 +8448,6 @@ k_batt_curve_peak(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, in
 // ---------------------------------------------------------------------------
 constexpr int SWB_FATAL = DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_YEARS | DGEN_ST_HOURLY_FORM;
 
-__device__ __forceinline__ void swb_store(const dgen_swb_out& S, int64_t i, const BcPoint& a) {
-    if (S.npv) S.npv[i] = a.npv;
-    if (S.payback_raw) S.payback_raw[i] = a.payback;
-    if (S.total_cost) S.total_cost[i] = a.cost;
-    if (S.bank_kwh) S.bank_kwh[i] = a.bank;
-    if (S.power_kw) S.power_kw[i] = a.power;
-    if (S.bill_w_year1) S.bill_w_year1[i] = a.w1;
-    if (S.bill_wo_year1) S.bill_wo_year1[i] = a.wo1;
-    if (S.lifetime_savings) S.lifetime_savings[i] = a.life;
-    if (S.tariff) S.tariff[i] = a.tariff;
-    if (S.switched) S.switched[i] = a.switched;
-    S.status[i] = a.status;
-}
-
 // The objective: -npv of the point, its members in `a`.  A point that cannot
 // be valued leaves NaN members, its status in a.status (a bit of SWB_FATAL)
 // and returns NaN.  The caller has checked tariff0 and the economic life.
@@ -8652,13 +8643,33 @@ __device__ __forceinline__ double swb_point(const dgen_tables& T, const dgen_age
     return -a.npv;
 }
 
-__global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
-k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, const double* __restrict__ lo_p,
-            const double* __restrict__ hi_p, double ratio, double hours, int trace_n, dgen_swb_out S) {
-    const int64_t i = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int PH = lds_half(T.max_periods);
-    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BC_BLOCK]
+// the three searches' bracket: the caller's, or k_size_w's (ff:440-444)
+__device__ __forceinline__ void swb_bracket(const dgen_tables& T, const dgen_agents& A, int64_t i,
+                                            const double* __restrict__ lo_p, const double* __restrict__ hi_p,
+                                            double& low, double& high) {
+    if (lo_p) {
+        low = lo_p[i];
+        high = hi_p[i];
+    } else {
+        const double max_load = A.load_kwh[i] / T.cf_naep[A.cf_row[i]];
+        low = max_load * 0.8;
+        high = max_load * 1.25;
+    }
+}
+
+// The search of agent i over [low, high]; eval(x, a) values one point (the
+// objective, the point's members in `a`).  status: the agent's own bits,
+// joined to every stored point; a bit of SWB_FATAL among them flags the agent
+// at (t0, not switched) without an evaluation.  k_size_batt's rule alone can
+// pass one: the net and peak kernels skip such agents before they get here,
+// and their status is DGEN_ST_ZERO_LOAD or 0.  The members are stored whenever an evaluation becomes the
+// search's best point (brent_bounded's own rule: the first one, then
+// fu <= fx), so after the search they are the bits of the evaluation at the x
+// it returns.  An evaluation that cannot be valued ends the lane: its NaN
+// members and status are stored and every later request returns at once.
+template <class Eval>
+__device__ __forceinline__ void swb_search(const dgen_swb_out& S, int64_t i, int trace_n, double low, double high,
+                                           int status, int t0, Eval&& eval) {
     const double q = __builtin_nan("");
     double* const tx = (trace_n > 0 && S.trace_x) ? S.trace_x + i * trace_n : nullptr;
     double* const tf = (trace_n > 0 && S.trace_f) ? S.trace_f + i * trace_n : nullptr;
@@ -8666,39 +8677,16 @@ k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, 
         if (tx) tx[k] = q;
         if (tf) tf[k] = q;
     }
-    const int t0 = A.tariff0[i];
-    const int N = A.econ_life[i];
-    int status = 0;
-    if (N < 1 || N > MAXY) status |= DGEN_ST_YEARS;
-    if (t0 < 0 || t0 >= T.n_tariffs) status |= DGEN_ST_TARIFF;
-    else if (T.tariffs[t0].flags & DGEN_ST_UNIT) status |= DGEN_ST_HOURLY_FORM;   // an agent the sizing call leaves unsized
-    double low, high;
-    if (lo_p) {
-        low = lo_p[i];
-        high = hi_p[i];
-    } else {                                                         // k_size_w's bracket (ff:440-444)
-        const double max_load = A.load_kwh[i] / T.cf_naep[A.cf_row[i]];
-        low = max_load * 0.8;
-        high = max_load * 1.25;
+    if (S.system_kw) S.system_kw[i] = q;
+    if (status & SWB_FATAL) {
+        bc_store(S, i, bc_nan_point(t0, 0, status), true);
+        if (S.nfev) S.nfev[i] = 0;
+        return;
     }
     const double span = high - low;
     const double tl = (span > 1.0 ? span : 1.0) * 1e-3;
     const double fl_tl = floor(tl);
     const double xatol = fl_tl < 2.0 ? 2.0 : fl_tl;
-    if (!isfinite(low) || !isfinite(high) || !(low > 0.0) || !(low < high)) status |= DGEN_ST_BOUNDS;
-    if (A.load_kwh[i] == 0.0) status |= DGEN_ST_ZERO_LOAD;
-    if (S.system_kw) S.system_kw[i] = q;
-    if (status & SWB_FATAL) {
-        const BcPoint z = {q, q, q, q, q, q, q, q, t0, 0, status};
-        swb_store(S, i, z);
-        if (S.nfev) S.nfev[i] = 0;
-        return;
-    }
-    // The members are stored whenever an evaluation becomes the search's best
-    // point (brent_bounded's own rule: the first one, then fu <= fx), so after
-    // the search they are the bits of the evaluation at the x it returns.  An
-    // evaluation that cannot be valued ends the lane: its NaN members and
-    // status are stored and every later request returns at once.
     int cnt = 0;
     bool dead = false;
     double best = 0.0;
@@ -8708,7 +8696,7 @@ k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, 
         [&](double x) __attribute__((always_inline)) {
             if (dead) return q;
             BcPoint a;
-            const double f = swb_point(T, A, cfg, i, batt_on, lds, PH, x, ratio, hours, a);
+            const double f = eval(x, a);
             if (cnt < trace_n) {
                 if (tx) tx[cnt] = x;
                 if (tf) tf[cnt] = f;
@@ -8717,7 +8705,7 @@ k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, 
             if (dead || cnt == 0 || f <= best) {
                 best = f;
                 a.status |= status;
-                swb_store(S, i, a);
+                bc_store(S, i, a, true);
             }
             cnt += 1;
             return f;
@@ -8725,6 +8713,29 @@ k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, 
         low, high, xatol, &nfev, &x_last);
     if (S.system_kw && !dead) S.system_kw[i] = kw;
     if (S.nfev) S.nfev[i] = cnt;
+}
+
+__global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_size_batt(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, const double* __restrict__ lo_p,
+            const double* __restrict__ hi_p, double ratio, double hours, int trace_n, dgen_swb_out S) {
+    const int64_t i = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int PH = lds_half(T.max_periods);
+    double* const lds = dyn_lds + threadIdx.x;             // plane b, period p at [(b * PH + p) * BC_BLOCK]
+    // ---- the agent's own rule: whatever ends it is flagged and stored ----
+    const int t0 = A.tariff0[i];
+    const int N = A.econ_life[i];
+    int status = 0;
+    if (N < 1 || N > MAXY) status |= DGEN_ST_YEARS;
+    if (t0 < 0 || t0 >= T.n_tariffs) status |= DGEN_ST_TARIFF;
+    else if (T.tariffs[t0].flags & DGEN_ST_UNIT) status |= DGEN_ST_HOURLY_FORM;   // an agent the sizing call leaves unsized
+    double low, high;
+    swb_bracket(T, A, i, lo_p, hi_p, low, high);
+    if (!isfinite(low) || !isfinite(high) || !(low > 0.0) || !(low < high)) status |= DGEN_ST_BOUNDS;
+    if (A.load_kwh[i] == 0.0) status |= DGEN_ST_ZERO_LOAD;
+    swb_search(S, i, trace_n, low, high, status, t0, [&](double x, BcPoint& a) __attribute__((always_inline)) {
+        return swb_point(T, A, cfg, i, batt_on, lds, PH, x, ratio, hours, a);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -8768,6 +8779,24 @@ __device__ __forceinline__ SwnBank swn_bank(const dgen_tables& T, const dgen_age
         }
     }
     return b;
+}
+
+__device__ __forceinline__ bool peak_form(const dgen_tables& T, const dgen_cfg& cfg, const dgen_tariff& t) {
+    return peak_unit(t) || tariff_demand(T, cfg, t) != nullptr;
+}
+
+// The form an evaluation at x is billed under, sb = swn_bank(x): 2 the peak
+// form, 1 options 2 and 3 without peaks, 0 swb_point's -- the bins form
+// valued, every other point flagged by its rules.
+__device__ __forceinline__ int swb_form(const dgen_tables& T, const dgen_cfg& cfg, int PH, double x, double ratio,
+                                        double hours, const SwnBank& sb) {
+    const double kwh = x / ratio, kwp = kwh / hours;
+    if (kwh >= 0.0 && !isinf(kwh) && (!(kwh > 0.0) || (kwp > 0.0 && !isinf(kwp))) && sb.tariff >= 0 &&
+        sb.tariff < T.n_tariffs) {
+        const dgen_tariff& t = T.tariffs[sb.tariff];
+        if (t.P >= 1 && t.P <= PH && t.T >= 1 && t.T <= MAXT) return peak_form(T, cfg, t) ? 2 : net_hourly(t) ? 1 : 0;
+    }
+    return 0;
 }
 
 // The objective under options 2 and 3: -npv of the dgen_batt_curve_net point,
@@ -9059,7 +9088,6 @@ k_size_batt_net(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_
     char* const wsb = ws + (size_t)blockIdx.x * bn_block_bytes(cap);
     double* const accw = reinterpret_cast<double*>(wsb) + threadIdx.x;
     BnEnt* const ent = reinterpret_cast<BnEnt*>(wsb + BN_ACC_BYTES) + threadIdx.x;
-    const double q = __builtin_nan("");
     const int64_t step = (int64_t)gridDim.x * BC_BLOCK;
     for (int64_t i = (int64_t)blockIdx.x * BC_BLOCK + threadIdx.x; i < n; i += step) {
         // ---- the candidate rule: from the tables and the agent's columns alone ----
@@ -9069,14 +9097,7 @@ k_size_batt_net(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_
         if (t0 < 0 || t0 >= T.n_tariffs) continue;
         if (T.tariffs[t0].flags & DGEN_ST_UNIT) continue;
         double low, high;
-        if (lo_p) {
-            low = lo_p[i];
-            high = hi_p[i];
-        } else {                                                         // k_size_batt's bracket (ff:440-444)
-            const double max_load = A.load_kwh[i] / T.cf_naep[A.cf_row[i]];
-            low = max_load * 0.8;
-            high = max_load * 1.25;
-        }
+        swb_bracket(T, A, i, lo_p, hi_p, low, high);
         if (!isfinite(low) || !isfinite(high) || !(low > 0.0) || !(low < high)) continue;
         bool net = net_hourly(T.tariffs[t0]);
         {
@@ -9089,57 +9110,16 @@ k_size_batt_net(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_
         }
         if (!net) continue;                     // no evaluation of this agent can bill hourly imports
         // ---- the search, as k_size_batt runs it ----
-        const double span = high - low;
-        const double tl = (span > 1.0 ? span : 1.0) * 1e-3;
-        const double fl_tl = floor(tl);
-        const double xatol = fl_tl < 2.0 ? 2.0 : fl_tl;
         const int status = A.load_kwh[i] == 0.0 ? DGEN_ST_ZERO_LOAD : 0;
-        double* const tx = (trace_n > 0 && S.trace_x) ? S.trace_x + i * trace_n : nullptr;
-        double* const tf = (trace_n > 0 && S.trace_f) ? S.trace_f + i * trace_n : nullptr;
-        for (int k = 0; k < trace_n; k++) {
-            if (tx) tx[k] = q;
-            if (tf) tf[k] = q;
-        }
-        if (S.system_kw) S.system_kw[i] = q;
-        int cnt = 0;
-        bool dead = false;
-        double best = 0.0;
-        int nfev = 0;
-        double x_last = 0.0;
-        const double kw = brent_bounded(
-            [&](double x) __attribute__((always_inline)) {
-                if (dead) return q;
-                BcPoint a;
-                double f;
-                const SwnBank sb = swn_bank(T, A, cfg, i, batt_on, x, ratio, hours);
-                const double kwh = x / ratio, kwp = kwh / hours;
-                bool net_form = kwh >= 0.0 && !isinf(kwh) && (!(kwh > 0.0) || (kwp > 0.0 && !isinf(kwp))) &&
-                                sb.tariff >= 0 && sb.tariff < T.n_tariffs;
-                if (net_form) {
-                    const dgen_tariff& t = T.tariffs[sb.tariff];
-                    net_form = t.P >= 1 && t.P <= PH && t.T >= 1 && t.T <= MAXT && net_hourly(t) && !peak_unit(t) &&
-                               tariff_demand(T, cfg, t) == nullptr;
-                }
-                // every other point is swb_point's: the bins form valued, the rest flagged by its rules
-                if (net_form) f = swn_point(T, A, cfg, i, lds, PH, x, sb, accw, ent, cap, a);
-                else f = swb_point(T, A, cfg, i, batt_on, lds, PH, x, ratio, hours, a);
-                if (cnt < trace_n) {
-                    if (tx) tx[cnt] = x;
-                    if (tf) tf[cnt] = f;
-                }
-                dead = (a.status & SWB_FATAL) != 0;
-                if (a.status & DGEN_ST_TARIFF) a.status |= DGEN_ST_HOURLY_FORM;   // every form that ends the agent
-                if (dead || cnt == 0 || f <= best) {
-                    best = f;
-                    a.status |= status;
-                    swb_store(S, i, a);
-                }
-                cnt += 1;
-                return f;
-            },
-            low, high, xatol, &nfev, &x_last);
-        if (S.system_kw && !dead) S.system_kw[i] = kw;
-        if (S.nfev) S.nfev[i] = cnt;
+        swb_search(S, i, trace_n, low, high, status, t0, [&](double x, BcPoint& a) __attribute__((always_inline)) {
+            const SwnBank sb = swn_bank(T, A, cfg, i, batt_on, x, ratio, hours);
+            double f;
+            if (swb_form(T, cfg, PH, x, ratio, hours, sb) == 1) f = swn_point(T, A, cfg, i, lds, PH, x, sb, accw, ent, cap, a);
+            else f = swb_point(T, A, cfg, i, batt_on, lds, PH, x, ratio, hours, a);
+            // every form that ends the agent; both bits are fatal, so swb_search's dead rule sees the same
+            if (a.status & DGEN_ST_TARIFF) a.status |= DGEN_ST_HOURLY_FORM;
+            return f;
+        });
     }
 }
 
@@ -9569,10 +9549,6 @@ __device__ __attribute__((noinline)) double swp_point(const dgen_tables& T, cons
     return -a.npv;
 }
 
-__device__ __forceinline__ bool peak_form(const dgen_tables& T, const dgen_cfg& cfg, const dgen_tariff& t) {
-    return peak_unit(t) || tariff_demand(T, cfg, t) != nullptr;
-}
-
 __global__ void __launch_bounds__(BC_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
 k_size_batt_peak(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, const double* __restrict__ lo_p,
                  const double* __restrict__ hi_p, double ratio, double hours, int trace_n, dgen_swb_out S,
@@ -9658,7 +9634,7 @@ k_size_batt_peak(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt
                 if (dead || cnt == 0 || f <= best) {
                     best = f;
                     a.status |= status;
-                    swb_store(S, i, a);
+                    bc_store(S, i, a, true);
                 }
                 cnt += 1;
                 return f;
