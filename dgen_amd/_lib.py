@@ -145,6 +145,15 @@ BILL_FIELDS = ["energy_charge", "export_credit", "fixed_charge", "demand_flat", 
                "import_kwh", "export_kwh", "billed_kwh", "peak_kw"]
 
 
+REPLAY_PLANES = ["baseline", "pvonly", "with_batt"]   # include/dgen_hip.h dgen_replay_planes
+
+
+class ReplayPlanes(ctypes.Structure):
+    """dgen_replay_planes: hour-quad tiled [NH / 4][n][4] device planes (any may be NULL), float32 or
+    float64 (f64 = 1)."""
+    _fields_ = [(name, _vp) for name in REPLAY_PLANES] + [("f64", _i32), ("pad", _i32)]
+
+
 class BillOpt(ctypes.Structure):
     """dgen_bill_opt: battery = 1 bills the scan's peak-shaving dispatch at the given kW."""
     _fields_ = [("battery", _i32), ("pad", _i32)]
@@ -236,7 +245,7 @@ EXPORTED = [
     "dgen_finance_series", "dgen_year_inputs", "dgen_initial_market_shares", "dgen_rows_seq_sum",
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
     "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
-    "dgen_size_with_batt", "dgen_size_with_batt_net", "dgen_size_with_batt_peak",
+    "dgen_size_with_batt", "dgen_size_with_batt_net", "dgen_size_with_batt_peak", "dgen_replay_at",
 ]
 
 
@@ -350,6 +359,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_size_with_batt_peak.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _i64, _vp, _vp,
                                            ctypes.POINTER(SwbOpt), ctypes.POINTER(SwbPeakOpt), ctypes.POINTER(SwbOut),
                                            _vp]
+    L.dgen_replay_at.restype = _i32
+    L.dgen_replay_at.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _vp, _vp, _vp, _i64,
+                                 ctypes.POINTER(BattSummaryOpt), ctypes.POINTER(BattSummaryOut),
+                                 ctypes.POINTER(ReplayPlanes), _vp, _vp, _vp, _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

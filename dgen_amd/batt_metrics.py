@@ -14,6 +14,10 @@ module carries that up:
     state_monthly(...)                    per segment and month MWh of the kWh members
     annual_columns(engine, batch, out)    the per-agent columns of the drop-in switch
                                           (financial_functions.size_frame(batt_metrics=True))
+    replay_outputs(engine, batch, kw, bank_kwh, bank_kw)
+                                          the summary (and planes) at a caller-given PV size
+                                          and bank (Engine.replay_at), caller order
+    replay_columns(d, cfg, prefix)        annual_columns of a replay_outputs result
 
 Nothing here reads an hourly value on the host: no plane is needed at all, so
 the metrics are the same bits in every hourly mode.  The reference's
@@ -67,6 +71,36 @@ def summary_outputs(engine, batch, out, want: Optional[Sequence[str]] = None,
     if inv is None:
         return d
     return {k: v.index_select(1, inv) for k, v in d.items()}
+
+
+def replay_outputs(engine, batch, kw, bank_kwh, bank_kw=None, want: Optional[Sequence[str]] = None,
+                   midday=_lib.BATT_SUMMARY_MIDDAY, planes=None) -> Dict[str, object]:
+    """Engine.replay_at in caller order: the dispatch replayed with kw[k] kW of
+    PV and a bank of bank_kwh[k] kWh / bank_kw[k] kW (None: bank_kwh / 2) for
+    caller row k -- the point a what-if call priced (batt_sizing.best_point,
+    Engine.size_with_batt), not only the reference's kW / 0.8 at 2 h.  The [n]
+    inputs (host arrays or device tensors) are laid out in the batch's device
+    order (batch.perm) for the call and the results gathered back:
+    {member: [12, n]} like summary_outputs, plus bank_kwh, power_kw (the bank
+    as sized, what annual() takes) and status, each [n].  planes ("f32" /
+    "f64"): baseline, pvonly and with_batt come back as the hour-quad tiles
+    [NH / 4, n, 4] with their columns still in the batch's device order, the
+    form Engine.plane_digest and attachment.state_hourly take."""
+    import torch
+    perm = batch.perm
+    pt = None if perm is None else engine._to_dev(np.asarray(perm, np.int64), torch.int64)
+
+    def dev_order(v):
+        if v is None:
+            return None
+        t = engine._to_dev(v, torch.float64)
+        return t if pt is None else t.index_select(0, pt)
+
+    d = engine.replay_at(batch, dev_order(kw), dev_order(bank_kwh), dev_order(bank_kw), want, midday, planes)
+    inv = _inverse(engine, perm)
+    if inv is None:
+        return d
+    return {k: v if k in _lib.REPLAY_PLANES else v.index_select(v.dim() - 1, inv) for k, v in d.items()}
 
 
 def annual(d: Dict[str, object], bank_kwh, cfg) -> Dict[str, object]:
@@ -177,4 +211,19 @@ def annual_columns(engine, batch, out, midday=_lib.BATT_SUMMARY_MIDDAY) -> Dict[
         if t.dtype == torch.int32:
             t = t.to(torch.int64)
         res[PREFIX + k] = t.cpu().numpy()
+    return res
+
+
+def replay_columns(d: Dict[str, object], cfg, prefix: str = PREFIX) -> Dict[str, np.ndarray]:
+    """annual_columns for a replay: the per-agent columns (prefix + each of
+    ANNUAL) of replay_outputs' result `d` as host arrays in d's order --
+    annual() with the bank the replay sized (d["bank_kwh"]), float64 except the
+    hour counts (int64)."""
+    a = annual({k: d[k] for k in _lib.BATT_SUMMARY_FIELDS}, d["bank_kwh"], cfg)
+    res = {}
+    for k in ANNUAL:
+        t = a[k]
+        if not isinstance(t, np.ndarray):
+            t = t.cpu().numpy()
+        res[prefix + k] = t.astype(np.int64) if t.dtype == np.int32 else t
     return res

@@ -58,6 +58,59 @@ INVALID = (_lib.ST_BOUNDS | _lib.ST_TARIFF | _lib.ST_YEARS | _lib.ST_SCRATCH | _
 CO_PREFIX = "pvb_opt_"
 CO_COLUMNS = tuple(CO_PREFIX + k for k in ("kw", "kwh", "batt_kw", "npv", "payback", "nfev", "status", "npv_gain"))
 
+# the spec key "dispatch": True of either switch: the 22 batt_diag_ quantities
+# (batt_metrics.ANNUAL) of the dispatch replayed at the chosen point
+# (Engine.replay_at), batt_opt_diag_* and pvb_opt_diag_*
+DIAG_PREFIX = PREFIX + "diag_"
+CO_DIAG_PREFIX = CO_PREFIX + "diag_"
+
+
+def _diag_names(prefix):
+    from .batt_metrics import ANNUAL
+    return tuple(prefix + k for k in ANNUAL)
+
+
+def dispatch(spec) -> bool:
+    """True when the spec (of either switch) asks for the dispatch at the
+    chosen point: a dict with "dispatch": True."""
+    return isinstance(spec, dict) and bool(spec.get("dispatch", False))
+
+
+def columns_of(spec) -> Tuple[str, ...]:
+    """The columns size_frame(batt_sizing=spec) adds: COLUMNS, and the 22
+    batt_opt_diag_* after them with "dispatch": True."""
+    return COLUMNS + (_diag_names(DIAG_PREFIX) if dispatch(spec) else ())
+
+
+def co_columns_of(spec) -> Tuple[str, ...]:
+    """The columns size_frame(pv_batt_sizing=spec) adds: CO_COLUMNS, and the 22
+    pvb_opt_diag_* after them with "dispatch": True."""
+    return CO_COLUMNS + (_diag_names(CO_DIAG_PREFIX) if dispatch(spec) else ())
+
+
+def diag_columns(engine, batch, kw, bank_kwh, bank_kw, valid, prefix) -> Dict[str, np.ndarray]:
+    """The 22 diag columns of a chosen point as host arrays in caller order:
+    batt_metrics.replay_columns of Engine.replay_at at kw / bank_kwh / bank_kw
+    ([n] device tensors in the batch's device order).  valid: [n] bool, the
+    agents that have a point; the others (and any the replay flags) are
+    replayed at kw = 0 without a bank and hold NaN in the float columns and 0
+    in the hour counts, as the sibling *_opt_ columns do."""
+    import torch
+    from . import batt_metrics as bm
+    zero = torch.zeros_like(kw)
+    d = engine.replay_at(batch, torch.where(valid, kw, zero), torch.where(valid, bank_kwh, zero),
+                         torch.where(valid, bank_kw, torch.ones_like(kw)))
+    ok = valid & (d["status"] == 0)
+    inv = _inverse(engine, batch.perm)
+    if inv is not None:
+        d = {k: v.index_select(v.dim() - 1, inv) for k, v in d.items()}
+        ok = ok.index_select(0, inv)
+    cols = bm.replay_columns(d, engine.cfg, prefix)
+    okh = ok.cpu().numpy()
+    for k, v in cols.items():
+        v[~okh] = np.nan if v.dtype.kind == "f" else 0
+    return cols
+
 
 def _xp(t):
     if isinstance(t, np.ndarray):
@@ -197,14 +250,16 @@ def summarize(curve: Dict[str, object], ref_point: int) -> Dict[str, object]:
 def grid(spec) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
     """size_frame's batt_sizing spec as (pv_to_batt, hours): a dict with either
     key, a (pv_to_batt, hours) pair, or True for the default grid.  The dict's
-    "net_billing" and "peak_billing" keys are not part of the grid
-    (net_billing(spec), peak_billing(spec))."""
+    "net_billing", "peak_billing" and "dispatch" keys are not part of the grid
+    (net_billing(spec), peak_billing(spec), dispatch(spec))."""
     if spec is True:
         return (0.4, 0.8, 1.6), (1.0, 2.0, 4.0)
     if isinstance(spec, dict):
-        bad = set(spec) - {"pv_to_batt", "hours", "net_billing", "peak_billing"}
+        bad = set(spec) - {"pv_to_batt", "hours", "net_billing", "peak_billing", "dispatch"}
         if bad:
             raise ValueError(f"batt_sizing: unknown keys {sorted(bad)}")
+        if not isinstance(spec.get("dispatch", False), (bool, np.bool_)):
+            raise ValueError(f"batt_sizing: dispatch must be a bool (got {spec['dispatch']!r})")
         return tuple(spec.get("pv_to_batt", (REF_PV_TO_BATT,))), tuple(spec.get("hours", (REF_HOURS,)))
     r, h = spec
     return tuple(r), tuple(h)
@@ -230,7 +285,10 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     batt_opt_status (int64).  Only these [n] vectors cross to the host.  With
     "net_billing": True in the spec the net-billing points are computed too
     (dgen_batt_curve_net), with "peak_billing": True the points on tariffs
-    with billed demand charges or kWh/kW tier units (dgen_batt_curve_peak)."""
+    with billed demand charges or kWh/kW tier units (dgen_batt_curve_peak).
+    With "dispatch": True the 22 batt_opt_diag_* columns follow (columns_of):
+    the dispatch replayed at kW* with the best point's desired kWh and kW as
+    the curve was handed them (diag_columns)."""
     import torch
     r, h = grid(spec)
     skw = out["system_kw"]
@@ -251,6 +309,10 @@ def annual_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
         if t.dtype == torch.int32:
             t = t.to(torch.int64)
         res[k] = t.cpu().numpy()
+    if dispatch(spec):
+        idx = s[PREFIX + "point"]
+        res.update(diag_columns(engine, batch, skw, _pick(torch, kwh, idx, 0.0), _pick(torch, kw, idx, 1.0),
+                                idx >= 0, DIAG_PREFIX))
     return res
 
 
@@ -263,13 +325,14 @@ def co_size_spec(spec, peak: bool = False) -> Tuple[float, float]:
     both must be finite and positive.  The dict's "net_billing", "net_cap" and
     "net_blocks" keys are not part of the pair (co_size_options(spec)).  The
     keys it admits without `peak` are the ones it always admitted; peak=True
-    (what co_size_options and co_size_columns pass) also admits PEAK_KEYS,
-    which are not part of the pair either."""
+    (what co_size_options and co_size_columns pass) also admits PEAK_KEYS and
+    "dispatch", which are not part of the pair either."""
     if spec is True:
         return REF_PV_TO_BATT, REF_HOURS
     if not isinstance(spec, dict):
         raise ValueError(f"pv_batt_sizing: True or a dict with \"ratio\" / \"hours\" (got {spec!r})")
-    bad = set(spec) - {"ratio", "hours", "net_billing", "net_cap", "net_blocks"} - set(PEAK_KEYS if peak else ())
+    bad = (set(spec) - {"ratio", "hours", "net_billing", "net_cap", "net_blocks"}
+           - set(PEAK_KEYS + ("dispatch",) if peak else ()))
     if bad:
         raise ValueError(f"pv_batt_sizing: unknown keys {sorted(bad)}")
     r, h = float(spec.get("ratio", REF_PV_TO_BATT)), float(spec.get("hours", REF_HOURS))
@@ -288,10 +351,13 @@ def co_size_options(spec) -> Dict[str, object]:
     "peak_billing": True gives {"peak": True} with "peak_caps" (a pair
     (cap_mixed, cap_kept) of ints, 1 .. _lib.NB_CAPM and 1 ..
     _lib.BATT_PEAK_CAPK_MAX, None in either place: the default) and
-    "peak_blocks" (>= 1); neither key implies the other."""
+    "peak_blocks" (>= 1); neither key implies the other.  "dispatch" must be
+    a bool and is no keyword of the search (dispatch(spec))."""
     co_size_spec(spec, peak=True)
     if spec is True:
         return {}
+    if not isinstance(spec.get("dispatch", False), (bool, np.bool_)):
+        raise ValueError(f"pv_batt_sizing: dispatch must be a bool (got {spec['dispatch']!r})")
     net = spec.get("net_billing", False)
     if not isinstance(net, (bool, np.bool_)):
         raise ValueError(f"pv_batt_sizing: net_billing must be a bool (got {net!r})")
@@ -367,7 +433,10 @@ def co_size_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
     the host.  With "net_billing": True in the spec the agents on net-billing
     tariffs are searched too (dgen_size_with_batt_net; co_size_options(spec)), with
     "peak_billing": True those on billed demand charges and kWh/kW tier units
-    (dgen_size_with_batt_peak)."""
+    (dgen_size_with_batt_peak).  With "dispatch": True the 22
+    pvb_opt_diag_* columns follow (co_columns_of): the dispatch replayed at
+    pvb_opt_kw with the bank the search sized from it, x / ratio kWh at
+    (x / ratio) / hours kW (diag_columns)."""
     import torch
     r, h = co_size_spec(spec, peak=True)
     d = engine.size_with_batt(batch, r, h, want=("system_kw", "bank_kwh", "power_kw", "npv", "payback_raw", "nfev",
@@ -380,4 +449,9 @@ def co_size_columns(engine, batch, out, spec=True) -> Dict[str, np.ndarray]:
         if t.dtype == torch.int32:
             t = t.to(torch.int64)
         res[k] = t.cpu().numpy()
+    if dispatch(spec):
+        x = d["system_kw"]
+        e = x / r
+        ok = ((d["status"] & INVALID) == 0) & torch.isfinite(x)
+        res.update(diag_columns(engine, batch, x, e, e / h, ok, CO_DIAG_PREFIX))
     return res

@@ -6901,6 +6901,191 @@ k_batt_summary(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64
 }
 
 // ---------------------------------------------------------------------------
+// Dispatch replay at a caller-given PV size and bank (dgen_replay_at; the
+// definition is in include/dgen_hip.h): k_batt_summary's walk of the year --
+// lane per agent, the day-ahead 16-B row loads, the scan's own device
+// functions on operands formed the same way -- with kW and the desired bank
+// read from the caller's columns instead of a sizing call's outputs.
+// SUM: the month accumulators and the [12][n] summary, as k_batt_summary.
+// PLN: the three hourly planes (PT float or double) in the scan's hour-quad
+// tiles, one rp_store (non-temporal 16-B stores) per plane, lane and four
+// hours; a form without SUM carries no accumulator, so its registers go to
+// the three staging quads.  Every value either form writes is computed by
+// the same expressions on the same operands, so a member or a plane has the
+// same bits whichever instantiation wrote it (no contraction, no cross-lane
+// traffic).  A flagged lane (kW or bank out of bounds) writes zeros and
+// leaves; the branch is divergent, the rest of the wave walks the year.
+// ---------------------------------------------------------------------------
+// One lane's hour quad into a tile row, non-temporal like the scan's planes
+// (nobody in the call reads them back), as plain vector stores the compiler
+// sees (it forms a 64-bit lane address, global_store_dwordx4 v[a:a+1], v[..],
+// off nt): it counts the stores in its vmcnt waits -- the next day's row
+// loads are waited for without draining the day's stores -- and keeps the two
+// wait states a VALU write of the stored registers needs after a store of
+// more than 64 bits (an inline-asm store is invisible to that hazard check,
+// and here the staging registers are reused right after the store).
+__device__ __forceinline__ void rp_store(char* row, uint32_t off, const float (&q)[4]) {
+    const f32x4 v = {q[0], q[1], q[2], q[3]};
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(row + off));
+}
+__device__ __forceinline__ void rp_store(char* row, uint32_t off, const double (&q)[4]) {
+    const f64x2 a = {q[0], q[1]}, b = {q[2], q[3]};
+    f64x2* const p = reinterpret_cast<f64x2*>(row + off);
+    __builtin_nontemporal_store(a, p);
+    __builtin_nontemporal_store(b, p + 1);
+}
+
+template <bool SUM, bool PLN, typename PT>
+__global__ void __launch_bounds__(BS_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+k_replay_at(dgen_tables T, dgen_agents A, dgen_cfg cfg, int64_t n, int batt_on, uint32_t midmask,
+            const double* __restrict__ kw_in, const double* __restrict__ kwh_in,
+            const double* __restrict__ pkw_in, dgen_batt_summary_out S, dgen_replay_planes P,
+            double* bank_out, double* power_out, int32_t* status_out) {
+    const int64_t i = (int64_t)blockIdx.x * BS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    // the planes' tile rows: wave-uniform bases, the lane's 32-bit byte offset
+    // (host guarantees n < 2^27)
+    constexpr uint32_t QB = sizeof(PT) * 4;
+    char* const ob = reinterpret_cast<char*>(P.baseline);
+    char* const op = reinterpret_cast<char*>(P.pvonly);
+    char* const ow = reinterpret_cast<char*>(P.with_batt);
+    const uint32_t off16 = (uint32_t)i * QB;
+    const size_t row16 = (size_t)n * QB;
+    const double kw = kw_in[i];
+    const double desired_kwh = kwh_in[i];
+    const double desired_kw = pkw_in ? pkw_in[i] : desired_kwh / 2.0;
+    int status = 0;
+    if (!(kw >= 0.0) || isinf(kw)) status |= DGEN_ST_BOUNDS;
+    if (!(desired_kwh >= 0.0) || isinf(desired_kwh)) status |= DGEN_ST_BOUNDS;
+    else if (pkw_in && desired_kwh > 0.0 && (!(desired_kw > 0.0) || isinf(desired_kw))) status |= DGEN_ST_BOUNDS;
+    status_out[i] = status;
+    if (status) {
+        if constexpr (SUM) {
+            const BsMonth z = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0};
+            for (int m = 0; m < 12; m++) bs_month_store(S, (int64_t)m * n + i, z);
+        }
+        if constexpr (PLN) {
+            const PT z[4] = {(PT)0, (PT)0, (PT)0, (PT)0};
+            size_t q16 = 0;
+            for (int q = 0; q < NH / 4; q++) {
+                if (ob) rp_store(ob + q16, off16, z);
+                if (op) rp_store(op + q16, off16, z);
+                if (ow) rp_store(ow + q16, off16, z);
+                q16 += row16;
+            }
+        }
+        if (bank_out) bank_out[i] = 0.0;
+        if (power_out) power_out[i] = 0.0;
+        return;
+    }
+    const bool is_res = (A.flags[i] & 1) != 0;
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double kwh = A.load_kwh[i];
+    const double ls = kwh / T.shape_sum[lr];
+    const double cs6 = (((kw * 1000.0) * 0.96) / 1000.0) / 1e6;
+    const float* __restrict__ shp = T.shapes + (int64_t)lr * NH;
+    const int32_t* __restrict__ cfp = T.cfs + (int64_t)cr * NH;
+    double bank = 0.0, power = 0.0;
+    if (batt_on) batt_size(desired_kw, desired_kwh, is_res ? 240.0 : 500.0, cfg, &bank, &power);
+    const double inv_eta_in = 1.0 / cfg.batt_eta_in;
+    const double in_per_bank = bank > 0.0 ? cfg.batt_eta_in / bank : 0.0;
+    const double out_per_bank = bank > 0.0 ? 1.0 / (cfg.batt_eta_out * bank) : 0.0;
+    if (!(bank > 0.0)) power = 0.0;
+    if (bank_out) bank_out[i] = bank;
+    if (power_out) power_out[i] = power;
+    // the counts' thresholds (include/dgen_hip.h)
+    const double soc_hi = cfg.batt_max_soc - 1e-9, soc_lo = cfg.batt_min_soc + 1e-9;
+    const double pw_hi = power + 1e-6, pw_dis = power * (1.0 - 1e-9);
+    const bool has_pw = power > 0.0;
+    const bool mfl = cfg.batt_month_floor != 0;
+    double soc = cfg.batt_init_soc;
+    size_t q16 = 0;
+    PT qb[4], qp[4], qw[4];
+    BsDay cur, nxt;
+    bs_day_load(shp, cfp, 0, cur);
+    for (int m = 0; m < 12; m++) {
+        BsMonth a = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY, 0.0, 0, 0, 0, 0, 0, 0};
+        double mfloor = 0.0;
+        for (int d = c_month_start_day[m]; d < c_month_start_day[m + 1]; d++) {
+            // the next day's rows, ahead of this day's sort (December 31 loads itself again)
+            bs_day_load(shp, cfp, d < 364 ? d + 1 : 364, nxt);
+            double dv[24];
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++)
+                dv[hh] = fmax((double)cur.s[hh >> 2][hh & 3] * ls - (double)cur.c[hh >> 2][hh & 3] * cs6, 0.0);
+            sort24_desc(dv);
+            const double avail0 = fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+            double target = day_target_sorted(dv, power, avail0);
+            {   // dgen_cfg.batt_month_floor: the month's target never falls
+                const double tf = target < mfloor ? mfloor : target;
+                target = mfl ? tf : target;
+                mfloor = mfl ? tf : mfloor;
+            }
+            // load and PV again from the raw day (opaque: see k_batt_summary)
+            const double ls2 = opaque(ls), cs2 = opaque(cs6);
+#pragma unroll
+            for (int hh = 0; hh < 24; hh++) {
+                const double ld = (double)opaque_f(cur.s[hh >> 2][hh & 3]) * ls2;
+                const double pv = (double)opaque_i(cur.c[hh >> 2][hh & 3]) * cs2;
+                const double nn = ld - pv;
+                const double soc0 = soc;
+                const HourStep hs = batt_hour(nn, pv, target, power, bank, soc, cfg, inv_eta_in, in_per_bank,
+                                              out_per_bank);
+                if constexpr (SUM) {
+                    // the hour's flows: batt_hour's clamps at the pre-hour SOC
+                    const bool chg = nn < 0.0;
+                    const double room = fmax((cfg.batt_max_soc - soc0) * bank * inv_eta_in, 0.0);
+                    const double avail = fmax((soc0 - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
+                    const double cc = chg ? fmin(fmin(-nn, power), room) : 0.0;
+                    const double dd = chg ? 0.0 : fmin(fmin(fmax(nn - target, 0.0), power), avail);
+                    const double sur = fmax(-nn, 0.0);
+                    const double p2g = sur - cc;
+                    const bool mid = ((midmask >> hh) & 1u) != 0;      // wave-uniform
+                    a.pv += pv;
+                    a.sur += sur;
+                    a.p2b += cc;
+                    a.p2g += p2g;
+                    a.p2l += fmin(ld, pv);
+                    a.b2l += dd;
+                    a.g2l += hs.g2l;
+                    a.sur_m += mid ? sur : 0.0;
+                    a.p2b_m += mid ? cc : 0.0;
+                    a.p2g_m += mid ? p2g : 0.0;
+                    a.smin = fmin(a.smin, soc);
+                    a.smax = fmax(a.smax, soc);
+                    const bool full = soc >= soc_hi;
+                    a.hc += cc > 0.0;
+                    a.hd += dd > 0.0;
+                    a.hsb += sur > 1e-6 && full;
+                    a.hpb += sur > pw_hi && soc < soc_hi;
+                    a.he += nn > 1e-6 && soc <= soc_lo;
+                    a.hdp += dd > pw_dis && has_pw;
+                } else {
+                    (void)soc0;
+                }
+                if constexpr (PLN) {
+                    // the scan's plane values with one size for both runs
+                    qb[hh & 3] = (PT)ld;
+                    qp[hh & 3] = (PT)fmax(nn, 0.0);
+                    qw[hh & 3] = (PT)hs.g2l;
+                    if ((hh & 3) == 3) {
+                        if (ob) rp_store(ob + q16, off16, qb);
+                        if (op) rp_store(op + q16, off16, qp);
+                        if (ow) rp_store(ow + q16, off16, qw);
+                        q16 += row16;
+                    }
+                }
+            }
+            cur = nxt;
+        }
+        if constexpr (SUM) {
+            a.send = soc;
+            bs_month_store(S, (int64_t)m * n + i, a);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Year-1 monthly bill breakdown (dgen_bill_months; the definition is in
 // include/dgen_hip.h): the oracle's bin_year / year_bill / year_demand at
 // degradation and escalation factor 1, month by month, for one agent per lane
@@ -11171,6 +11356,78 @@ int32_t dgen_batt_summary(dgen_ctx* c, const dgen_tables* T, const dgen_agents* 
     HIP_TRY(hipSetDevice(c->device));
     hipLaunchKernelGGL(k_batt_summary, dim3((unsigned)blocks), dim3(BS_BLOCK), 0, (hipStream_t)stream, *T, *A, *O,
                        c->cfg, n, c->battery, midmask, *out);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_replay_at(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const double* kw,
+                       const double* bank_kwh, const double* bank_kw, int64_t n, const dgen_batt_summary_opt* opt,
+                       const dgen_batt_summary_out* summary, const dgen_replay_planes* planes, double* bank_out,
+                       double* power_out, int32_t* status, void* stream) {
+    if (!c || !T || !A || !kw || !bank_kwh || !status || n < 0) {
+        set_err("dgen_replay_at: null argument or negative n");
+        return DGEN_E_ARG;
+    }
+    if (!summary && !planes) {
+        set_err("dgen_replay_at: neither a summary nor planes asked for");
+        return DGEN_E_ARG;
+    }
+    if (!T->shapes || !T->shape_sum || !T->cfs || !T->tariffs || T->n_tariffs <= 0 ||
+        (T->n_demand > 0 && !T->demand)) {
+        set_err("dgen_replay_at: incomplete tables");
+        return DGEN_E_ARG;
+    }
+    if (!A->load_row || !A->cf_row || !A->load_kwh || !A->flags) {
+        set_err("dgen_replay_at: missing agent column (load_row, cf_row, load_kwh, flags)");
+        return DGEN_E_ARG;
+    }
+    if (c->cfg.batt_update_hours == 1 || c->cfg.batt_loss_model == 1) {
+        set_err("dgen_replay_at: the hourly re-plan (batt_update_hours = 1) and the Li-ion loss model "
+                "(batt_loss_model = 1) are not replayed: the daily plan under constant efficiencies only");
+        return DGEN_E_ARG;
+    }
+    const int lo = opt ? opt->mid_lo : 11, hi = opt ? opt->mid_hi : 15;
+    if (lo < 0 || hi > 23 || lo > hi) {
+        set_err("dgen_replay_at: midday window [%d, %d] must satisfy 0 <= mid_lo <= mid_hi <= 23", lo, hi);
+        return DGEN_E_ARG;
+    }
+    if (planes && (planes->f64 < 0 || planes->f64 > 1)) {
+        set_err("dgen_replay_at: planes->f64 must be 0 (float32) or 1 (float64)");
+        return DGEN_E_ARG;
+    }
+    // a lane stores its hour quad as 16-B vectors
+    if (planes && ((((uintptr_t)planes->baseline | (uintptr_t)planes->pvonly | (uintptr_t)planes->with_batt) & 15u) != 0)) {
+        set_err("dgen_replay_at: the planes must be 16-byte aligned");
+        return DGEN_E_ARG;
+    }
+    // the kernel forms a 32-bit per-lane byte offset i x 32 into the fp64 tiles
+    if (planes && n >= ((int64_t)1 << 27)) {
+        set_err("dgen_replay_at: n = %lld with planes (limit 2^27 - 1)", (long long)n);
+        return DGEN_E_ARG;
+    }
+    const int64_t blocks = (n + BS_BLOCK - 1) / BS_BLOCK;
+    if (blocks > 0x7fffffff) {
+        set_err("dgen_replay_at: n = %lld exceeds the launch grid", (long long)n);
+        return DGEN_E_ARG;
+    }
+    if (n == 0) return DGEN_OK;
+    uint32_t midmask = 0;
+    for (int k = lo; k <= hi; k++) midmask |= 1u << k;
+    HIP_TRY(hipSetDevice(c->device));
+    const dim3 grid((unsigned)blocks), blk(BS_BLOCK);
+    const dgen_batt_summary_out s0 = summary ? *summary : dgen_batt_summary_out{};
+    const dgen_replay_planes p0 = planes ? *planes : dgen_replay_planes{};
+    // the summary and the planes each walk the year in a form of their own
+    // (registers: DESIGN.md section 5); a value has the same bits from either
+    if (summary)
+        hipLaunchKernelGGL((k_replay_at<true, false, float>), grid, blk, 0, (hipStream_t)stream, *T, *A, c->cfg, n,
+                           c->battery, midmask, kw, bank_kwh, bank_kw, s0, p0, bank_out, power_out, status);
+    if (planes && p0.f64)
+        hipLaunchKernelGGL((k_replay_at<false, true, double>), grid, blk, 0, (hipStream_t)stream, *T, *A, c->cfg, n,
+                           c->battery, midmask, kw, bank_kwh, bank_kw, s0, p0, bank_out, power_out, status);
+    else if (planes)
+        hipLaunchKernelGGL((k_replay_at<false, true, float>), grid, blk, 0, (hipStream_t)stream, *T, *A, c->cfg, n,
+                           c->battery, midmask, kw, bank_kwh, bank_kw, s0, p0, bank_out, power_out, status);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

@@ -732,6 +732,68 @@ class Engine:
                                               self.stream_handle()), "dgen_batt_summary")
         return res
 
+    def replay_at(self, batch: AgentBatch, kw, bank_kwh, bank_kw=None, want=None,
+                  midday=_lib.BATT_SUMMARY_MIDDAY, planes=None) -> Dict[str, object]:
+        """The dispatch of `batch` replayed with kw[j] kW of PV and a battery of
+        bank_kwh[j] kWh / bank_kw[j] kW for device row j -- dgen_replay_at,
+        async on the current stream: batt_summary's months and the scan's three
+        hourly planes at a point a what-if call (batt_curve, size_with_batt)
+        priced, from the profile rows alone (no outputs of a sizing call).  kw,
+        bank_kwh, bank_kw: device tensors or host arrays of batch.n values in
+        the batch's device order (batch.perm maps caller rows to it); bank_kw
+        None: the reference's 2-hour bank (bank_kwh / 2); bank_kwh 0 is valid
+        (no bank), as is kw 0.  want: the summary members to compute (default
+        all of _lib.BATT_SUMMARY_FIELDS; an empty sequence: none, with planes);
+        midday: as in batt_summary.  planes: None (no plane), "f32" or "f64".
+        Returns {member: [12, n] device tensor, month-major} plus bank_kwh and
+        power_kw ([n] float64, the bank as sized), status ([n] int32: 0 or
+        _lib.ST_BOUNDS, whose rows hold 0 everywhere) and, with planes, the
+        hour-quad tiled [NH / 4, n, 4] tensors baseline, pvonly and with_batt
+        as alloc_outputs makes them, all in the batch's device order.  The
+        definitions are in include/dgen_hip.h."""
+        torch = _torch()
+        want = tuple(_lib.BATT_SUMMARY_FIELDS if want is None else want)
+        bad = [k for k in want if k not in _lib.BATT_SUMMARY_FIELDS]
+        if bad:
+            raise ValueError(f"replay_at: want must name members of {_lib.BATT_SUMMARY_FIELDS} (got {want})")
+        if planes not in (None, "f32", "f64"):
+            raise ValueError(f"replay_at: planes must be None, 'f32' or 'f64' (got {planes!r})")
+        if not want and planes is None:
+            raise ValueError("replay_at: neither summary members nor planes asked for")
+        lo, hi = (int(v) for v in midday)
+        if not 0 <= lo <= hi <= 23:
+            raise ValueError(f"replay_at: midday must be 0 <= lo <= hi <= 23 (got {tuple(midday)})")
+        n = batch.n
+        cols = [self._to_dev(v, torch.float64).contiguous() for v in (kw, bank_kwh)]
+        cols.append(None if bank_kw is None else self._to_dev(bank_kw, torch.float64).contiguous())
+        for c in cols:
+            if c is not None and (c.dim() != 1 or c.numel() != n):
+                raise ValueError(f"replay_at: kw, bank_kwh and bank_kw must hold one value per agent ({n}), "
+                                 f"got {tuple(c.shape)}")
+        res = {k: torch.empty((12, n), dtype=torch.float64 if k in _lib.BATT_SUMMARY_F64 else torch.int32,
+                              device=self.dev) for k in want}
+        so = _lib.BattSummaryOut(**{k: _ptr(v) for k, v in res.items()})
+        res["bank_kwh"] = torch.empty(n, dtype=torch.float64, device=self.dev)
+        res["power_kw"] = torch.empty(n, dtype=torch.float64, device=self.dev)
+        res["status"] = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        po = None
+        if planes is not None:
+            dt = torch.float64 if planes == "f64" else torch.float32
+            for k in _lib.REPLAY_PLANES:
+                res[k] = torch.empty((_lib.NH // 4, n, 4), dtype=dt, device=self.dev)
+            po = _lib.ReplayPlanes(*[_ptr(res[k]) for k in _lib.REPLAY_PLANES], int(planes == "f64"), 0)
+        if n == 0:
+            return res
+        opt = _lib.BattSummaryOpt(lo, hi)
+        _lib.check(self.lib.dgen_replay_at(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                           _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), n, ctypes.byref(opt),
+                                           ctypes.byref(so) if want else None,
+                                           None if po is None else ctypes.byref(po), _ptr(res["bank_kwh"]),
+                                           _ptr(res["power_kw"]), _ptr(res["status"]), self.stream_handle()),
+                   "dgen_replay_at")
+        self._keep["_replay"] = cols          # alive until the next call (stream order)
+        return res
+
     def bill_months(self, batch: AgentBatch, kw, tariff=None, battery: bool = False,
                     want=None) -> Dict[str, object]:
         """Year-1 monthly bill breakdown of `batch` at kw[j] kW under tariff[j]

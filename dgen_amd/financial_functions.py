@@ -329,12 +329,12 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         for name in BILL_COLUMNS:
             o[name] = np.concatenate([p[name] for p in parts])
     if batt_sizing is not None:
-        from .batt_sizing import COLUMNS as SIZING_COLUMNS
-        for name in SIZING_COLUMNS:
+        from .batt_sizing import columns_of
+        for name in columns_of(batt_sizing):
             o[name] = np.concatenate([p[name] for p in parts])
     if pv_batt_sizing is not None:
-        from .batt_sizing import CO_COLUMNS
-        for name in CO_COLUMNS:
+        from .batt_sizing import co_columns_of
+        for name in co_columns_of(pv_batt_sizing):
             o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
         if not keep_planes:
@@ -656,8 +656,11 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     bills hourly imports (metering options 2 and 3: every CA agent and the
     net-billing tariffs; dgen_batt_curve_net), which otherwise carry
     batt_opt_point = -1; its key "peak_billing": True those whose tariff bills
-    demand charges or has kWh/kW tier units (dgen_batt_curve_peak).  None (the
-    default) leaves the frame unchanged.  pv_batt_sizing: True, or a dict with
+    demand charges or has kWh/kW tier units (dgen_batt_curve_peak); its key
+    "dispatch": True adds the 22 batt_diag_ quantities of the dispatch
+    replayed at the best point (kW* with that point's bank; Engine.replay_at,
+    dgen_replay_at) as batt_opt_diag_*, NaN (hour counts 0) where
+    batt_opt_point is -1.  None (the default) leaves the frame unchanged.  pv_batt_sizing: True, or a dict with
     "ratio" and / or "hours" (batt_sizing.co_size_spec; the reference's 0.8 and
     2.0 otherwise) -- adds the eight columns batt_sizing.CO_COLUMNS: the PV size
     that maximises the with-battery NPV when the bank is sized from it (x /
@@ -672,7 +675,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     tariffs; dgen_size_with_batt_net), with "net_cap" and "net_blocks" that
     entry's options, and "peak_billing": True those on billed demand charges
     or kWh/kW tier units (dgen_size_with_batt_peak, issued last), with
-    "peak_caps" and "peak_blocks" (batt_sizing.co_size_options).  No plane is read: the
+    "peak_caps" and "peak_blocks" (batt_sizing.co_size_options); "dispatch":
+    True adds the dispatch replayed at pvb_opt_kw with the bank sized from it
+    as pvb_opt_diag_* (22 columns; NaN, hour counts 0, where the search is
+    invalid).  No plane is read: the
     same bits in every hourly mode and sub-batching.  None (the default) leaves
     the frame unchanged."""
     import time
@@ -773,12 +779,12 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
         for name in BILL_COLUMNS:
             out[name] = o[name]
     if batt_sizing is not None:
-        from .batt_sizing import COLUMNS as SIZING_COLUMNS
-        for name in SIZING_COLUMNS:
+        from .batt_sizing import columns_of
+        for name in columns_of(batt_sizing):
             out[name] = o[name]
     if pv_batt_sizing is not None:
-        from .batt_sizing import CO_COLUMNS
-        for name in CO_COLUMNS:
+        from .batt_sizing import co_columns_of
+        for name in co_columns_of(pv_batt_sizing):
             out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:

@@ -1384,6 +1384,71 @@ int32_t dgen_size_with_batt_peak(dgen_ctx* ctx, const dgen_tables* tables, const
                                  const double* lo, const double* hi, const dgen_swb_opt* opt,
                                  const dgen_swb_peak_opt* popt, const dgen_swb_out* out, void* stream);
 
+/* Dispatch replay at a caller-given PV size and bank (additive to ABI 14):
+ * dgen_batt_summary's monthly summary and the scan's three hourly planes for
+ * "agent i with kw[i] kW of PV and a battery of bank_kwh[i] kWh / bank_kw[i]
+ * kW", the point a what-if call (dgen_batt_curve, dgen_size_with_batt) priced.
+ * A replay from the profile rows: no dgen_outputs, no workspace, and tariff
+ * state plays no part.  kw, bank_kwh: [n] device doubles; bank_kw: [n] or NULL
+ * (then desired_kw = bank_kwh / 2.0, the reference's 2-hour bank, exactly as
+ * in dgen_batt_curve); status: [n] device int32; all but bank_kw required.
+ * bank_out, power_out: [n] device doubles, either may be NULL.  At least one
+ * of `summary` and `planes` must be non-NULL.  One lane per agent, the year in
+ * hour order.  Per agent i:
+ *   ls  = load_kwh / shape_sum[load_row]
+ *   cs6 = (((kw x 1000) x 0.96) / 1000) / 1e6
+ *   bank, power = battery_model_sizing(desired_kw, bank_kwh, 240 V residential
+ *                 | 500 V) as the scan sizes it (a positive bank_kwh below half
+ *                 a string still buys one string); 0, 0 for bank_kwh = 0 (a
+ *                 valid point: no bank) and after dgen_set_battery(0)
+ *   soc = batt_init_soc
+ * and for every hour h of the non-leap year, in order, dgen_batt_summary's
+ * hour operation for operation: ld, pv, nn; at h % 24 == 0 the day's
+ * peak-shaving target over the day's max(nn, 0) with the energy available at
+ * this SOC (raised to the month's largest earlier target with
+ * batt_month_floor); the scan's hour for soc and g2l; cc, dd and sur from the
+ * pre-hour SOC.
+ * summary: dgen_batt_summary_out's 19 members with their definitions above,
+ * month-major [12][n]; a NULL member is not written; the midday window is
+ * opt's (NULL: 11, 15).
+ * planes: the scan's values with one size for both runs,
+ *   baseline = ld;  pvonly = max(ld - pv, 0);  with_batt = g2l
+ * each rounded to float when f64 == 0, in the hour-quad tiles of dgen_outputs'
+ * hourly planes (the layout dgen_state_hourly and dgen_plane_digest take); a
+ * NULL plane is not written.  At kw = system_kw and bank_kwh = system_kw / 0.8
+ * (bank_kw NULL) the summary is dgen_batt_summary's and the planes are
+ * dgen_eval_agents' at that size, bit for bit.
+ * status[i]: 0, or DGEN_ST_BOUNDS when kw is not finite or is negative (kw = 0
+ * is valid: no PV, the bank never charges), when bank_kwh is not finite or is
+ * negative, or when bank_kw is given and is not finite or not positive while
+ * bank_kwh > 0 (dgen_batt_curve's rule).  A flagged agent gets 0 in every
+ * summary member, in its plane values and in bank_out / power_out, as
+ * dgen_batt_summary treats a skipped agent; no other agent's bits change.
+ * DGEN_ST_UNIT, _TARIFF and _YEARS do not arise.
+ * bank_out, power_out: bank and power as sized (dgen_batt_curve's bank_kwh and
+ * power_kw at the same point).
+ * The daily plan under the constant efficiencies only: batt_update_hours == 1
+ * or batt_loss_model == 1 returns DGEN_E_ARG, as does a window with mid_lo >
+ * mid_hi or outside 0..23, planes->f64 outside 0..1, a plane that is not
+ * 16-byte aligned (a lane stores its hour quad as 16-B vectors), and n >= 2^27
+ * when planes are given (the lane's 32-bit tile offset).  Table and agent-column checks
+ * are dgen_batt_summary's.  No atomics and no cross-lane traffic: run-to-run
+ * identical, and agent i's results do not depend on n or on its neighbours.
+ * A call that asks for the summary and the planes runs the year once for each
+ * (two launches on `stream`); every value has the bits of the call that asks
+ * for it alone.                                                             */
+typedef struct {           /* hour-quad tiles: (h, i) at ((h / 4) * n + i) * 4 + h % 4; 16-byte aligned; any may be NULL */
+    void *baseline, *pvonly, *with_batt;
+    int32_t f64;           /* 0: float32 planes, 1: float64 */
+    int32_t pad;
+} dgen_replay_planes;
+
+int32_t dgen_replay_at(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                       const double* kw, const double* bank_kwh, const double* bank_kw, int64_t n,
+                       const dgen_batt_summary_opt* opt, const dgen_batt_summary_out* summary,
+                       const dgen_replay_planes* planes, double* bank_out, double* power_out,
+                       int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
