@@ -226,6 +226,18 @@ class SwbPeakOpt(ctypes.Structure):
     _fields_ = [("cap_mixed", _i32), ("cap_kept", _i32), ("max_blocks", _i32), ("pad", _i32)]
 
 
+TRACE_MAX = 32   # include/dgen_hip.h DGEN_TRACE_MAX
+TRACE_ROWS = ["x", "f", "f_bound", "x_bound"]            # [n][TRACE_MAX] float64
+TRACE_F64 = TRACE_ROWS + ["model", "system_kw"]          # model [n][4], system_kw [n]
+TRACE_I32 = ["nfev", "certified", "undecided_at"]        # [n] int32
+TRACE_FIELDS = TRACE_F64 + TRACE_I32
+
+
+class SearchTraceOut(ctypes.Structure):
+    """dgen_search_trace_out: agent-major device buffers, any may be NULL."""
+    _fields_ = [(name, _vp) for name in TRACE_FIELDS]
+
+
 class DgenError(RuntimeError):
     pass
 
@@ -246,6 +258,7 @@ EXPORTED = [
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
     "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
     "dgen_size_with_batt", "dgen_size_with_batt_net", "dgen_size_with_batt_peak", "dgen_replay_at",
+    "dgen_search_trace",
 ]
 
 
@@ -363,6 +376,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_replay_at.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), _vp, _vp, _vp, _i64,
                                  ctypes.POINTER(BattSummaryOpt), ctypes.POINTER(BattSummaryOut),
                                  ctypes.POINTER(ReplayPlanes), _vp, _vp, _vp, _vp]
+    L.dgen_search_trace.restype = _i32
+    L.dgen_search_trace.argtypes = [_vp, ctypes.POINTER(Tables), ctypes.POINTER(Agents), ctypes.POINTER(Outputs),
+                                    _i64, ctypes.POINTER(SearchTraceOut), _vp]
     if L.dgen_abi_version() != ABI_VERSION:
         raise DgenError("libdgen_hip.so ABI version mismatch")
     _LIB = L

@@ -5423,13 +5423,21 @@ __device__ __forceinline__ bool bt_sure_eq(double u, double du, int pu, double v
 // bt_replay's undecided comparisons by kind (DGEN_PHASE_PROF builds: phase
 // slots 1 switch thresholds / x order / final x's, 2 fu vs fx, 3 the other
 // point updates, 7 the termination tests, 8 the parabolic step's tests)
+// AUDIT (k_search_trace): evaluation k's bounds -- dfu, of |f_device -
+// f_oracle| there, and dx, of |x_device - x_oracle| -- go to f_bound[k] /
+// x_bound[k] (either may be null) once the evaluation is taken, and *stop gets
+// the evaluations taken when the replay ended (nfev where it certified, or
+// failed only the closing tests); no phase counters.  k_brent_certify runs
+// AUDIT = false: the three pointers are not read.
 #if DGEN_PHASE_PROF
-#define BT_FAIL(k) do { atomicAdd(&g_phase[k], 1ull); return false; } while (0)
+#define BT_FAIL(k) do { if constexpr (AUDIT) *stop = num; else atomicAdd(&g_phase[k], 1ull); return false; } while (0)
 #else
-#define BT_FAIL(k) return false
+#define BT_FAIL(k) do { if constexpr (AUDIT) *stop = num; return false; } while (0)
 #endif
+template <bool AUDIT>
 __device__ bool bt_replay(const double* __restrict__ f, int nfev, double x1, double x2, double xatol,
-                          const BtModel& M, const dgen_switch* sw, int sw_cnt) {
+                          const BtModel& M, const dgen_switch* sw, int sw_cnt, double* f_bound = nullptr,
+                          double* x_bound = nullptr, int* stop = nullptr) {
     const double sqrt_eps = 1.4832396974191326e-08;
     const double golden_mean = 0.3819660112501051;
     double a = x1, b = x2, da = 0.0, db = 0.0;
@@ -5450,6 +5458,10 @@ __device__ bool bt_replay(const double* __restrict__ f, int nfev, double x1, dou
         const double fu = f[num];
         const double dfu = M.c0 + M.c1 * fabs(x) + M.ce * fabs(fu) + M.lip * dx;
         const int px = num;
+        if constexpr (AUDIT) {
+            if (f_bound) f_bound[px] = dfu;
+            if (x_bound) x_bound[px] = dx;
+        }
         dx_last = dx;
         num += 1;
         if (num == 1) {
@@ -5583,6 +5595,7 @@ __device__ bool bt_replay(const double* __restrict__ f, int nfev, double x1, dou
     // under the bound (the decisions above fix the path; the observed
     // differences of certified agents are ~1e-13)
     if (dxf > 1e-7 * fmax(1.0, fabs(xf)) || dx_last > 1e-7 * fmax(1.0, fabs(x))) BT_FAIL(1);
+    if constexpr (AUDIT) *stop = num;
     return true;
 }
 
@@ -5610,6 +5623,98 @@ __device__ void bt_prices(const dgen_tables& T, const dgen_cfg& cfg, int tix, do
     if (cfg.skip_demand_charges == 0 && t.dc > 0) pmdc = INFINITY;   // no bound without the table
 }
 
+// What the replay of agent i's search needs: k_size's bracket and xatol, the
+// solar switch rows and the error model of its objective.  ok: the model is
+// usable (finite, every bound table it needs present, every switch row inside
+// the tariff table).  The one construction of the model: k_brent_certify
+// decides with it and k_search_trace (dgen_search_trace) lays it open.
+struct BtSearch {
+    double low, high, xatol;
+    const dgen_switch* sw;
+    int sw_cnt;
+    BtModel M;
+    bool ok;
+};
+
+__device__ BtSearch bt_search_of(const dgen_tables& T, const dgen_agents& A, const dgen_cfg& cfg, int64_t i) {
+    const int N = A.econ_life[i];
+    const double kwh = A.load_kwh[i];
+    const int lr = A.load_row[i], cr = A.cf_row[i];
+    const double naep0 = T.cf_naep[cr];
+    const double max_load = kwh / naep0;               // k_size's bracket
+    const double low = max_load * 0.8, high = max_load * 1.25;
+    const double span = high - low;
+    const double tl = (span > 1.0 ? span : 1.0) * 1e-3;
+    const double fl_tl = floor(tl);
+    const double xatol = fl_tl < 2.0 ? 2.0 : fl_tl;
+    // prices of every tariff the search can bill with
+    double pm = fabs(cfg.nm_yearend_sell_rate), pmdc = 0.0, pku = 0.0, otc = 0.0;
+    bool mo2 = false;
+    const int t0 = A.tariff0[i];
+    bt_prices(T, cfg, t0, pm, pmdc, pku, mo2);
+    const dgen_switch* sw = T.switches + A.sw_solar_off[i];
+    const int sw_cnt = A.sw_solar_cnt[i];
+    bool ok = true;
+    for (int r = 0; r < sw_cnt; r++) {
+        const int tt = sw[r].tariff;
+        if (tt < 0 || tt >= T.n_tariffs) { ok = false; break; }
+        bt_prices(T, cfg, tt, pm, pmdc, pku, mo2);
+        otc = fmax(otc, fabs(sw[r].one_time_charge));
+    }
+    const bool is_ca = (A.flags[i] & 2) != 0;
+    const int wr = A.wholesale_row[i];
+    if (mo2 && !is_ca && wr >= 0 && T.wholesale) {
+        if (!T.bt_ts_max) ok = false;
+        else pm = fmax(pm, T.bt_ts_max[wr] * fabs(A.price_mult[i]) * (1.0 + 1e-6));
+    }
+    // discounted escalation over the analysis period, D = sum_y rr^y
+    // (1 + infl + esc)^(y - 1), and the largest degradation factor
+    const double infl = A.inflation[i], real = A.real_discount[i];
+    const double rr = 1.0 / ((1.0 + real) * (1.0 + infl));
+    const double rb = fabs(1.0 + infl + A.escalator[i]);
+    const double sb = fabs(1.0 - A.pv_deg[i]);
+    double D = 0.0, dr = 1.0, er = 1.0, smax = 1.0, sy = 1.0;
+    for (int y = 1; y <= N && y <= MAXY; y++) {
+        dr *= rr;
+        D += dr * er;
+        er *= rb;
+        smax = fmax(smax, sy);
+        sy *= sb;
+    }
+    D *= 1.01;
+    // peak load (kW) and per-kW generation of the agent's rows
+    const double S = T.shape_sum[lr];
+    const double lmax = T.bt_shape_max ? T.bt_shape_max[lr] * fabs(kwh / S) : INFINITY;
+    const double gmax = T.bt_cf_max ? T.bt_cf_max[cr] * 1e-6 : INFINITY;
+    const double capc = fabs(A.capex[i] * A.ccm[i]);
+    const double dem = pmdc + pku;                    // $/kW a month of peak
+    const double g = BT_GAMMA * BT_EPS;
+    BtModel M;
+    // bills (BT_GAMMA's model): 2 x price x (load + generation) a
+    // year for the with-system bill and the no-system one; demand:
+    // 12 months x price x (peak load + generation at the peak hour)
+    // (4 x: a coarser bound, the extension mode only)
+    M.c0 = g * (2.0 * D * pm * 2.0 * fabs(kwh) + (dem > 0.0 ? 4.0 * D * dem * 24.0 * lmax : 0.0) + otc);
+    M.c1 = g * (2.0 * D * smax * 0.96 * pm * fabs(naep0) + (dem > 0.0 ? 4.0 * D * smax * 0.96 * dem * 12.0 * gmax : 0.0) +
+                4.0 * capc);
+    M.ce = g;
+    // Lipschitz: NPV moves by <= (3 + 0.02 D) x the cost change (the
+    // debt's payments at up to twice their principal, tax shields,
+    // insurance) and by <= 2 x price x generation of the bills
+    // (+10 %); demand: 12 months x price x generation per kW
+    M.lip = (3.0 + 0.02 * D) * capc + 2.2 * D * smax * 0.96 * pm * fabs(naep0) +
+            (dem > 0.0 ? 4.0 * D * smax * 0.96 * dem * 12.0 * gmax : 0.0);
+    // a missing TS bound table or a switch row outside the tariff table: no
+    // model (the prices above are then incomplete)
+    if (!ok) M.c0 = M.c1 = M.lip = NAN;
+    BtSearch R;
+    R.low = low; R.high = high; R.xatol = xatol;
+    R.sw = sw; R.sw_cnt = sw_cnt;
+    R.M = M;
+    R.ok = isfinite(M.c0) && isfinite(M.c1) && isfinite(M.lip) && isfinite(xatol);
+    return R;
+}
+
 // One thread per agent: replay its traced search, list it when not certain.
 // list[0] counts the chunk's listed agents, list[1 ..] their rows.
 __global__ void __launch_bounds__(256)
@@ -5623,75 +5728,9 @@ k_brent_certify(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int6
         if (nfev > 0 && !(st & (DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_UNIT | DGEN_ST_YEARS))) {
             flag = true;
             if (mode == 1 && nfev <= BT_MAX) {
-                const int N = A.econ_life[i];
-                const double kwh = A.load_kwh[i];
-                const int lr = A.load_row[i], cr = A.cf_row[i];
-                const double naep0 = T.cf_naep[cr];
-                const double max_load = kwh / naep0;               // k_size's bracket
-                const double low = max_load * 0.8, high = max_load * 1.25;
-                const double span = high - low;
-                const double tl = (span > 1.0 ? span : 1.0) * 1e-3;
-                const double fl_tl = floor(tl);
-                const double xatol = fl_tl < 2.0 ? 2.0 : fl_tl;
-                // prices of every tariff the search can bill with
-                double pm = fabs(cfg.nm_yearend_sell_rate), pmdc = 0.0, pku = 0.0, otc = 0.0;
-                bool mo2 = false;
-                const int t0 = A.tariff0[i];
-                bt_prices(T, cfg, t0, pm, pmdc, pku, mo2);
-                const dgen_switch* sw = T.switches + A.sw_solar_off[i];
-                const int sw_cnt = A.sw_solar_cnt[i];
-                bool ok = true;
-                for (int r = 0; r < sw_cnt; r++) {
-                    const int tt = sw[r].tariff;
-                    if (tt < 0 || tt >= T.n_tariffs) { ok = false; break; }
-                    bt_prices(T, cfg, tt, pm, pmdc, pku, mo2);
-                    otc = fmax(otc, fabs(sw[r].one_time_charge));
-                }
-                const bool is_ca = (A.flags[i] & 2) != 0;
-                const int wr = A.wholesale_row[i];
-                if (mo2 && !is_ca && wr >= 0 && T.wholesale) {
-                    if (!T.bt_ts_max) ok = false;
-                    else pm = fmax(pm, T.bt_ts_max[wr] * fabs(A.price_mult[i]) * (1.0 + 1e-6));
-                }
-                // discounted escalation over the analysis period, D = sum_y rr^y
-                // (1 + infl + esc)^(y - 1), and the largest degradation factor
-                const double infl = A.inflation[i], real = A.real_discount[i];
-                const double rr = 1.0 / ((1.0 + real) * (1.0 + infl));
-                const double rb = fabs(1.0 + infl + A.escalator[i]);
-                const double sb = fabs(1.0 - A.pv_deg[i]);
-                double D = 0.0, dr = 1.0, er = 1.0, smax = 1.0, sy = 1.0;
-                for (int y = 1; y <= N && y <= MAXY; y++) {
-                    dr *= rr;
-                    D += dr * er;
-                    er *= rb;
-                    smax = fmax(smax, sy);
-                    sy *= sb;
-                }
-                D *= 1.01;
-                // peak load (kW) and per-kW generation of the agent's rows
-                const double S = T.shape_sum[lr];
-                const double lmax = T.bt_shape_max ? T.bt_shape_max[lr] * fabs(kwh / S) : INFINITY;
-                const double gmax = T.bt_cf_max ? T.bt_cf_max[cr] * 1e-6 : INFINITY;
-                const double capc = fabs(A.capex[i] * A.ccm[i]);
-                const double dem = pmdc + pku;                    // $/kW a month of peak
-                const double g = BT_GAMMA * BT_EPS;
-                BtModel M;
-                // bills (BT_GAMMA's model): 2 x price x (load + generation) a
-                // year for the with-system bill and the no-system one; demand:
-                // 12 months x price x (peak load + generation at the peak hour)
-                // (4 x: a coarser bound, the extension mode only)
-                M.c0 = g * (2.0 * D * pm * 2.0 * fabs(kwh) + (dem > 0.0 ? 4.0 * D * dem * 24.0 * lmax : 0.0) + otc);
-                M.c1 = g * (2.0 * D * smax * 0.96 * pm * fabs(naep0) + (dem > 0.0 ? 4.0 * D * smax * 0.96 * dem * 12.0 * gmax : 0.0) +
-                            4.0 * capc);
-                M.ce = g;
-                // Lipschitz: NPV moves by <= (3 + 0.02 D) x the cost change (the
-                // debt's payments at up to twice their principal, tax shields,
-                // insurance) and by <= 2 x price x generation of the bills
-                // (+10 %); demand: 12 months x price x generation per kW
-                M.lip = (3.0 + 0.02 * D) * capc + 2.2 * D * smax * 0.96 * pm * fabs(naep0) +
-                        (dem > 0.0 ? 4.0 * D * smax * 0.96 * dem * 12.0 * gmax : 0.0);
-                if (ok && isfinite(M.c0) && isfinite(M.c1) && isfinite(M.lip) && isfinite(xatol))
-                    flag = !bt_replay(trace + i * BT_MAX, nfev, low, high, xatol, M, sw, sw_cnt);
+                const BtSearch S = bt_search_of(T, A, cfg, i);
+                if (S.ok)
+                    flag = !bt_replay<false>(trace + i * BT_MAX, nfev, S.low, S.high, S.xatol, S.M, S.sw, S.sw_cnt);
             }
         }
     }
@@ -5705,6 +5744,72 @@ k_brent_certify(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int6
         base = __shfl(base, lead, WAVE);
         if (flag) list[1 + base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
     }
+}
+
+// dgen_search_trace: one lane per agent lays open the fast search the last
+// sizing call traced.  brent_bounded itself runs again over the traced
+// objective values (the objective records its argument and hands back
+// trace[k]), so the x's are the search's own bits; then the audit form of
+// bt_replay stores the certificate's per-evaluation bounds and its mode-1
+// decision.  A search that asks for evaluation BT_MAX has no value to take: it
+// is fed +inf from there on (no later point is accepted, the bracket shrinks to
+// its end) and reported truncated, nfev = BT_MAX + 1, system_kw NaN.  Rows of
+// x / f beyond the evaluations and rows of the bounds from the replay's stop on
+// are NaN.  Every lane writes its own rows only: no atomics, nothing shared.
+static_assert(BT_MAX == DGEN_TRACE_MAX, "dgen_search_trace_out rows hold the kernels' trace");
+__global__ void __launch_bounds__(256)
+k_search_trace(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_t n,
+               const double* __restrict__ trace, dgen_search_trace_out R) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double* const rx = R.x ? R.x + i * BT_MAX : nullptr;
+    double* const rf = R.f ? R.f + i * BT_MAX : nullptr;
+    double* const rfb = R.f_bound ? R.f_bound + i * BT_MAX : nullptr;
+    double* const rxb = R.x_bound ? R.x_bound + i * BT_MAX : nullptr;
+    const int st = O.status[i];
+    int nfev = 0, cert = -1, stop = -1, rows = 0, brows = 0;
+    double kw = NAN, m0 = NAN, m1 = NAN, m2 = NAN, m3 = NAN;
+    if (O.nfev[i] > 0 && !(st & (DGEN_ST_BOUNDS | DGEN_ST_TARIFF | DGEN_ST_UNIT | DGEN_ST_YEARS))) {
+        const BtSearch S = bt_search_of(T, A, cfg, i);
+        const double* const f = trace + i * BT_MAX;
+        int k = 0;
+        double x_last = 0.0;
+        const double xf = brent_bounded(
+            [&](double x) {
+                const int e = k++;
+                if (e >= BT_MAX) return (double)INFINITY;
+                if (rx) rx[e] = x;
+                return f[e];
+            },
+            S.low, S.high, S.xatol, &nfev, &x_last);
+        if (k > BT_MAX) nfev = BT_MAX + 1;
+        else kw = xf;
+        rows = nfev < BT_MAX ? nfev : BT_MAX;
+        if (rf)
+            for (int e = 0; e < rows; e++) rf[e] = f[e];
+        m0 = S.M.c0; m1 = S.M.c1; m2 = S.M.ce; m3 = S.M.lip;
+        cert = 0;
+        stop = 0;
+        if (S.ok)
+            cert = bt_replay<true>(f, nfev, S.low, S.high, S.xatol, S.M, S.sw, S.sw_cnt, rfb, rxb, &stop) ? 1 : 0;
+        brows = stop;
+        if (cert) stop = -1;
+    }
+    for (int e = rows; e < BT_MAX; e++) {
+        if (rx) rx[e] = NAN;
+        if (rf) rf[e] = NAN;
+    }
+    for (int e = brows; e < BT_MAX; e++) {
+        if (rfb) rfb[e] = NAN;
+        if (rxb) rxb[e] = NAN;
+    }
+    if (R.model) {
+        R.model[4 * i] = m0; R.model[4 * i + 1] = m1; R.model[4 * i + 2] = m2; R.model[4 * i + 3] = m3;
+    }
+    if (R.system_kw) R.system_kw[i] = kw;
+    if (R.nfev) R.nfev[i] = nfev;
+    if (R.certified) R.certified[i] = cert;
+    if (R.undecided_at) R.undecided_at[i] = stop;
 }
 
 // ---------------------------------------------------------------------------
@@ -9940,6 +10045,7 @@ struct dgen_ctx {
     int lds_max = 65536;           // the device's LDS per work-group (hipDeviceAttributeMaxSharedMemoryPerBlock)
     double* bt_buf = nullptr;      // [n][BT_MAX] objective values
     size_t bt_cap = 0;
+    int64_t bt_n = 0;              // agents whose searches the last year-lane call traced into bt_buf (0: none)
     int32_t* ex_list = nullptr;    // chunk j: [i0 + j] count, then its rows
     size_t ex_list_cap = 0;
     int32_t* ex_next = nullptr;    // [MAXCH] the re-run's work counters (k_size_exact's next)
@@ -10358,6 +10464,7 @@ static int32_t size_or_eval(dgen_ctx* c, const dgen_tables* T, const dgen_agents
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_size_exact),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ex_lds));
     double* const bt = exact_on ? c->bt_buf : nullptr;
+    c->bt_n = exact_on ? n : 0;    // dgen_search_trace reads this call's traces
     // the re-run's grid: the blocks the device holds at once (work counter),
     // at most EX_BLOCKS scratch slots
     int ex_grid = EX_BLOCKS;
@@ -10939,6 +11046,27 @@ int32_t dgen_exact_count(dgen_ctx* c, int64_t* out) {
         HIP_TRY(hipMemcpy(&k, c->ex_list + c->ex_last_off[j], sizeof(int32_t), hipMemcpyDeviceToHost));
         *out += k;
     }
+    return DGEN_OK;
+}
+
+int32_t dgen_search_trace(dgen_ctx* c, const dgen_tables* T, const dgen_agents* A, const dgen_outputs* O,
+                          int64_t n, const dgen_search_trace_out* out, void* stream) {
+    if (!c || !T || !A || !O || !out) { set_err("dgen_search_trace: null argument"); return DGEN_E_ARG; }
+    if (c->bt_n <= 0 || !c->bt_buf) {
+        set_err("dgen_search_trace: the last sizing call on this context recorded no search trace "
+                "(dgen_set_exact 0, dgen_eval_agents, or no call yet)");
+        return DGEN_E_ARG;
+    }
+    if (n != c->bt_n) {
+        set_err("dgen_search_trace: n = %lld, the traced call sized %lld agents", (long long)n, (long long)c->bt_n);
+        return DGEN_E_ARG;
+    }
+    if (int32_t r = yl_check_args(T, A, "dgen_search_trace")) return r;
+    if (!O->nfev || !O->status) { set_err("dgen_search_trace: missing output column (nfev, status)"); return DGEN_E_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_search_trace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, *A,
+                       *O, c->cfg, n, c->bt_buf, *out);
+    HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }
 

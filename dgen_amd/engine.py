@@ -608,6 +608,33 @@ class Engine:
         _lib.check(self.lib.dgen_exact_count(self.ctx, ctypes.byref(v)), "dgen_exact_count")
         return int(v.value)
 
+    def search_trace(self, batch: AgentBatch, out: Dict[str, object], want=None) -> Dict[str, object]:
+        """The fast search of the last size() call -- of `batch`, into `out` --
+        laid open (dgen_search_trace; async on the current stream).  want: the
+        members to compute (_lib.TRACE_FIELDS, default all).  Returns device
+        tensors in the batch's row order: x, f, f_bound, x_bound [n, TRACE_MAX]
+        (the search's evaluations, and the certificate's bounds of |device -
+        reference| at each; NaN beyond), model [n, 4] (c0, c1, ce, lip),
+        system_kw [n] (float64), nfev, certified (1 settled by the bound, 0 not,
+        -1 no search) and undecided_at [n] (int32).  Raises DgenError when the
+        last sizing call on the engine recorded no trace (set_exact(0),
+        evaluate, no call yet) or was not this batch's size."""
+        torch = _torch()
+        want = tuple(_lib.TRACE_FIELDS if want is None else want)
+        bad = [k for k in want if k not in _lib.TRACE_FIELDS]
+        if bad or not want:
+            raise ValueError(f"search_trace: want must name members of {_lib.TRACE_FIELDS} (got {want})")
+        n = batch.n
+        shape = lambda k: (n, _lib.TRACE_MAX) if k in _lib.TRACE_ROWS else ((n, 4) if k == "model" else (n,))
+        res = {k: torch.empty(shape(k), dtype=torch.float64 if k in _lib.TRACE_F64 else torch.int32,
+                              device=self.dev) for k in want}
+        co = self.c_outputs(out)
+        to = _lib.SearchTraceOut(**{k: _ptr(v) for k, v in res.items()})
+        _lib.check(self.lib.dgen_search_trace(self.ctx, ctypes.byref(self.tables), ctypes.byref(batch.c_agents),
+                                              ctypes.byref(co), n, ctypes.byref(to), self.stream_handle()),
+                   "dgen_search_trace")
+        return res
+
     def kernel_times(self):
         """Average per-launch device time (ms) of the three sizing kernels over
         the calls since the last query, from HIP events on the launch stream."""

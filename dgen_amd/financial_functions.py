@@ -236,7 +236,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
                 net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                 hourly_device: bool = False, max_rows: Optional[int] = None, grid_metrics: bool = False,
                 keep_planes: bool = True, fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
-                bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
+                bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None, search_audit: bool = False):
     """Size the batch in sub-batches of at most max_rows agents (default
     device_rows_budget()): a frame larger than the device budget is cut into
     consecutive caller-order row ranges, each sized in its own device call
@@ -260,7 +260,8 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     device (batt_sizing.COLUMNS, per-agent values: the bits of one call).
     pv_batt_sizing: each sub-batch also sizes its PV on the with-battery
     objective (batt_sizing.CO_COLUMNS, per-agent values: the bits of one
-    call)."""
+    call).  search_audit: each sub-batch also lays open its fast search
+    (search_audit.COLUMNS, per-agent values: the bits of one call)."""
     n = len(cols["load_kwh"])
     if max_rows is None:
         max_rows = device_rows_budget(get_engine(), grid_metrics=grid_metrics, bill_metrics=bill_metrics)
@@ -269,7 +270,7 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
     try:
         return _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows,
                                 grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing,
-                                pv_batt_sizing)
+                                pv_batt_sizing, search_audit)
     except torch.cuda.OutOfMemoryError:
         # another worker on this device took the memory the budget counted on:
         # free this process's cached blocks and size in halves (down to 1024)
@@ -280,17 +281,18 @@ def _run_device(b: PopulationBuilder, cols, src: ProfileStore, timing: Optional[
         return _run_device(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows=smaller,
                            grid_metrics=grid_metrics, keep_planes=keep_planes, fixed_kw=fixed_kw,
                            batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing,
-                           pv_batt_sizing=pv_batt_sizing)
+                           pv_batt_sizing=pv_batt_sizing, search_audit=search_audit)
 
 
 def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_device, max_rows: int,
                      grid_metrics: bool = False, keep_planes: bool = True, fixed_kw=None,
-                     batt_metrics: bool = False, bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
+                     batt_metrics: bool = False, bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None,
+                     search_audit: bool = False):
     n = len(cols["load_kwh"])
     if n <= max_rows:
         return _run_device_once(b, cols, src, timing, net_weights, hourly_async, hourly_device,
                                 grid_metrics, keep_planes, fixed_kw, batt_metrics, bill_metrics, batt_sizing,
-                                pv_batt_sizing)
+                                pv_batt_sizing, search_audit)
     from .hourly_column import _Segments
     parts = []
     tm_sum: dict = {}
@@ -308,7 +310,8 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
                                       grid_metrics=grid_metrics, keep_planes=keep_planes,
                                       fixed_kw=None if fixed_kw is None else fixed_kw[lo:hi],
                                       batt_metrics=batt_metrics, bill_metrics=bill_metrics,
-                                      batt_sizing=batt_sizing, pv_batt_sizing=pv_batt_sizing))
+                                      batt_sizing=batt_sizing, pv_batt_sizing=pv_batt_sizing,
+                                      search_audit=search_audit))
         for k, v in tm.items():
             tm_sum[k] = tm_sum.get(k, 0.0) + v
     o = {}
@@ -336,6 +339,10 @@ def _run_device_rows(b, cols, src, timing, net_weights, hourly_async, hourly_dev
         from .batt_sizing import co_columns_of
         for name in co_columns_of(pv_batt_sizing):
             o[name] = np.concatenate([p[name] for p in parts])
+    if search_audit:
+        from .search_audit import COLUMNS as SEARCH_COLUMNS
+        for name in SEARCH_COLUMNS:
+            o[name] = np.concatenate([p[name] for p in parts])
     for name in _lib.OUTPUT_HOURLY:
         if not keep_planes:
             o[name] = None
@@ -359,7 +366,7 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
                      net_weights: Optional[Tuple[np.ndarray, np.ndarray]] = None, hourly_async: bool = False,
                      hourly_device: bool = False, grid_metrics: bool = False, keep_planes: bool = True,
                      fixed_kw: Optional[np.ndarray] = None, batt_metrics: bool = False,
-                     bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
+                     bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None, search_audit: bool = False):
     """Size the batch in one device call (fixed_kw: evaluate caller row i at
     fixed_kw[i] kW instead, Engine.evaluate); net_weights = (number_of_adopters, non-adopters) per
     caller row also returns o["net_sum_kw"], size_chunk's hourly aggregate
@@ -377,7 +384,10 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     batt_sizing: o also holds batt_sizing.COLUMNS, the best of the spec's
     battery banks per agent (Engine.batt_curve, caller order).
     pv_batt_sizing: o also holds batt_sizing.CO_COLUMNS, the PV size on the
-    with-battery objective (Engine.size_with_batt, caller order)."""
+    with-battery objective (Engine.size_with_batt, caller order).
+    search_audit: o also holds search_audit.COLUMNS, the fast search's
+    evaluations and the certificate's decision (Engine.search_trace, caller
+    order), taken right after the sizing call."""
     import time
     import torch
     from .attachment import state_hourly
@@ -395,6 +405,10 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
     else:
         kw = np.asarray(fixed_kw, np.float64)
         eng.evaluate(batch, out, kw if batch.perm is None else kw[batch.perm])
+    sa = None
+    if search_audit:
+        from .search_audit import audit_columns
+        sa = audit_columns(eng, batch, out)
     net = None
     if net_weights is not None:
         perm = batch.perm if batch.perm is not None else np.arange(batch.n)
@@ -452,6 +466,8 @@ def _run_device_once(b: PopulationBuilder, cols, src: ProfileStore, timing: Opti
         o.update(bsz)
     if pvb is not None:
         o.update(pvb)
+    if sa is not None:
+        o.update(sa)
     if timing is not None:
         timing.update(upload_s=t1 - t0, device_s=t2 - t1, download_s=time.perf_counter() - t2)
     return o
@@ -586,7 +602,7 @@ def _fixed_kw_values(df: pd.DataFrame, fixed_kw) -> np.ndarray:
 def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                timing: Optional[dict] = None, net_weights=None, max_rows: Optional[int] = None,
                grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
-               bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
+               bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None, search_audit: bool = False):
     """The batched form of calc_system_size_and_performance over a whole agent
     frame (what size_chunk needs), built by column: the frame is columnised
     at once (columnar.columnize_frame), sized in one device call, and the
@@ -680,11 +696,23 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
     as pvb_opt_diag_* (22 columns; NaN, hour counts 0, where the search is
     invalid).  No plane is read: the
     same bits in every hourly mode and sub-batching.  None (the default) leaves
-    the frame unchanged."""
+    the frame unchanged.  search_audit: the frame gains the four columns
+    search_audit.COLUMNS -- search_nfev_fast (evaluations of the fast search),
+    search_certified (1: the certificate's bound on |device - reference|
+    settled every decision of the search, 0: not, -1: no search),
+    search_rerun (certified == 0: the agent the default mode re-runs in the
+    reference's arithmetic) and search_bound_usd (that bound on the objective at
+    the evaluation that gave the fast search's size) -- from
+    Engine.search_trace (dgen_search_trace) after each sub-batch's sizing call;
+    it needs the search and its trace: not with fixed_kw, not with the
+    engine's exact_brent 0.  The same bits in every hourly mode and
+    sub-batching."""
     import time
     if rate_switch_table is None:
         raise AttributeError("'NoneType' object has no attribute 'loc' (rate_switch_table is required)")
     fixed = None if fixed_kw is None else _fixed_kw_values(df, fixed_kw)
+    if search_audit and fixed is not None:
+        raise ValueError("search_audit lays open the search: not available with fixed_kw")
     if pv_batt_sizing is False:
         pv_batt_sizing = None
     if pv_batt_sizing is not None:
@@ -701,7 +729,7 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
                     hourly_device=hourly == "device", max_rows=max_rows, grid_metrics=grid_metrics,
                     keep_planes=not (grid_metrics and hourly == "none"), fixed_kw=fixed,
                     batt_metrics=batt_metrics, bill_metrics=bill_metrics, batt_sizing=batt_sizing,
-                    pv_batt_sizing=pv_batt_sizing)
+                    pv_batt_sizing=pv_batt_sizing, search_audit=search_audit)
     t2 = time.perf_counter()
     ids = df["agent_id"].tolist() if "agent_id" in df else list(df.index)
     _raise_for_status(o["status"], ids)
@@ -786,6 +814,10 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
         from .batt_sizing import co_columns_of
         for name in co_columns_of(pv_batt_sizing):
             out[name] = o[name]
+    if search_audit:
+        from .search_audit import COLUMNS as SEARCH_COLUMNS
+        for name in SEARCH_COLUMNS:
+            out[name] = o[name]
     t3 = time.perf_counter()
     if timing is not None:
         # download_wait_s: time the frame assembly waited for the hourly planes
@@ -797,7 +829,7 @@ def size_frame(df: pd.DataFrame, con, rate_switch_table, hourly: str = "lazy",
 def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode="simple",
                hourly: str = "lazy", timing: Optional[dict] = None, max_rows: Optional[int] = None,
                grid_metrics: bool = False, fixed_kw=None, batt_metrics: bool = False,
-               bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None):
+               bill_metrics: bool = False, batt_sizing=None, pv_batt_sizing=None, search_audit: bool = False):
     """ff:1136 -- size a chunk; returns (df_out, agg) with
     agg["net_sum_kw"][h] = sum_agents adopter[h] * n_adopt + baseline[h] * (n_cust - n_adopt).
     grid_metrics: size_frame's 18 per-agent grid-exchange columns.  fixed_kw:
@@ -807,7 +839,9 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     bill_metrics: size_frame's 18 per-agent year-1 bill columns (bill_*).
     batt_sizing: size_frame's points spec (the seven batt_opt_* columns).
     pv_batt_sizing: size_frame's spec of the PV size on the with-battery
-    objective (the eight pvb_opt_* columns)."""
+    objective (the eight pvb_opt_* columns).  search_audit: size_frame's four
+    search_* columns (the fast search's evaluations and the certificate's
+    decision per agent)."""
     global _worker_conn
     if len(static_agents_df) == 0:
         return pd.DataFrame([]), {"mode": "simple", "n_hours": 0, "net_sum_kw": []}
@@ -822,7 +856,7 @@ def size_chunk(static_agents_df: pd.DataFrame, sectors, rate_switch_table, mode=
     df_out, o = size_frame(df, _worker_conn, rate_switch_table, hourly=hourly, timing=timing,
                            net_weights=(n_adopt, n_non), max_rows=max_rows, grid_metrics=grid_metrics,
                            fixed_kw=fixed_kw, batt_metrics=batt_metrics, bill_metrics=bill_metrics,
-                           batt_sizing=batt_sizing, pv_batt_sizing=pv_batt_sizing)
+                           batt_sizing=batt_sizing, pv_batt_sizing=pv_batt_sizing, search_audit=search_audit)
     df_out = df_out.drop(columns=[c for c in _DROP if c in df_out.columns])
     agg = {"mode": "simple", "n_hours": NH, "net_sum_kw": o["net_sum_kw"].tolist()}
     return df_out, agg

@@ -714,6 +714,58 @@ int32_t dgen_set_exact(dgen_ctx* ctx, int32_t mode);
  * (synchronises the ctx's stream work of that call).                         */
 int32_t dgen_exact_count(dgen_ctx* ctx, int64_t* out);
 
+/* Search trace and certificate audit of the sizing call (additive to ABI 14).
+ * Lays open the fast search of the last dgen_size_agents call on this ctx
+ * (modes 1 and 2 trace it; the trace lives in the ctx until the next sizing or
+ * evaluation call).  tables, agents, outputs and n are that call's, as
+ * dgen_hourly_planes takes them; run it on that call's stream, or after it.
+ * Per agent i, with K = DGEN_TRACE_MAX:
+ *   x, f        the evaluations of the fast search in order: scipy's bounded
+ *               Brent run again over the traced objective values from the
+ *               bracket and xatol of ff:440-444, so x[i][k] are the search's
+ *               own bits; NaN beyond nfev.
+ *   nfev,       of that replayed search -- not of `outputs`, which hold the
+ *   system_kw   reference-arithmetic re-run's values for the agents mode 1 / 2
+ *               re-ran.  A search that asks for evaluation K is truncated: nfev
+ *               = K + 1, system_kw NaN, certified 0, the first K rows filled.
+ *   model       c0, c1, ce, lip of the certificate's error model: at the same
+ *               x, |f_device - f_reference| <= c0 + c1 |x| + ce |f|, and
+ *               |f(x) - f(x')| <= lip |x - x'| between rate-switch thresholds.
+ *   f_bound,    evaluation k's bound of |f_device - f_reference| (the model at
+ *   x_bound     x[k] plus lip x x_bound[k]) and of |x_device - x_reference|, as
+ *               the certificate carried them to that evaluation.  Rows from
+ *               undecided_at on are NaN.
+ *   certified   1: every decision of the search is the reference's under the
+ *               bound (mode 1 keeps the fast search's path); 0: not settled
+ *               (mode 1 re-runs the agent) -- also for a model that is not
+ *               finite, a missing bound table, or a switch row outside the
+ *               tariff table; -1: no search.  The mode-1 decision whatever
+ *               mode the ctx is in.
+ *   undecided_at  evaluations taken when the certificate stopped at a decision
+ *               the bound does not settle (nfev: only the closing test of the
+ *               reported x's failed; 0: no usable model); -1 if certified.
+ * No search -- outputs.status carries DGEN_ST_BOUNDS, _TARIFF, _UNIT or
+ * _YEARS, or outputs.nfev is 0: certified -1, nfev 0, undecided_at -1, NaN
+ * elsewhere.  One lane per agent, no atomics: agent i's rows do not depend on
+ * n, its neighbours or the chunk pipeline.  DGEN_E_ARG when the last sizing /
+ * evaluation call on the ctx recorded no trace (mode 0, dgen_eval_agents, no
+ * call yet), when n is not that call's, or when out is NULL.  Replaces nothing
+ * in the reference (scipy's search keeps no trace).                          */
+#define DGEN_TRACE_MAX 32                 /* evaluations traced per search */
+typedef struct {                          /* any member may be NULL: not written */
+    double  *x, *f;                       /* [n][DGEN_TRACE_MAX] agent-major; NaN beyond nfev */
+    double  *f_bound, *x_bound;           /* [n][DGEN_TRACE_MAX] */
+    double  *model;                       /* [n][4]: c0, c1, ce, lip */
+    double  *system_kw;                   /* [n] */
+    int32_t *nfev;                        /* [n] */
+    int32_t *certified;                   /* [n]: 1, 0, -1 */
+    int32_t *undecided_at;                /* [n] */
+} dgen_search_trace_out;
+
+int32_t dgen_search_trace(dgen_ctx* ctx, const dgen_tables* tables, const dgen_agents* agents,
+                          const dgen_outputs* out, int64_t n, const dgen_search_trace_out* trace,
+                          void* stream);
+
 /* Per-agent monthly grid-exchange digest of one hourly plane (additive to
  * ABI 14).  `plane` is one of dgen_size_agents' hourly planes in its hour-quad
  * tiles ((h, i) at ((h / 4) * n + i) * 4 + h % 4; float, or double when
