@@ -258,7 +258,7 @@ EXPORTED = [
     "dgen_plane_digest", "dgen_eval_agents", "dgen_objective_curve", "dgen_batt_summary",
     "dgen_bill_months", "dgen_batt_curve", "dgen_batt_curve_net", "dgen_batt_curve_peak",
     "dgen_size_with_batt", "dgen_size_with_batt_net", "dgen_size_with_batt_peak", "dgen_replay_at",
-    "dgen_search_trace",
+    "dgen_search_trace", "dgen_share_selftest",
 ]
 
 
@@ -297,6 +297,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.dgen_brent_selftest.restype = _i32
     L.dgen_brent_selftest.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp,
                                       _vp, _vp]
+    L.dgen_share_selftest.restype = _i32
+    L.dgen_share_selftest.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]
     L.dgen_set_dc_prebuild.restype = _i32
     L.dgen_set_dc_prebuild.argtypes = [_vp, _i32]
     L.dgen_last_paths.restype = _i32

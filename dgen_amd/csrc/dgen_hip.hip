@@ -138,6 +138,107 @@ __device__ __forceinline__ double cf_per_kw_fast(int32_t x) {
 }
 
 // ---------------------------------------------------------------------------
+// The tiered bills' period shares u_p / U of a month (P <= PREG quotients by
+// one divisor) from one reciprocal, each equal to the IEEE quotient bit for
+// bit (tests/check_share_div.c; dgen_share_selftest on the device).
+//
+// recip_rn: the hardware seed (v_rcp_f64, about 2^-23 relative) squares its
+// error per Newton step y += y * (1 - U y): 2^-46, then 2^-92 before the
+// rounding, so two steps leave y within 1 ulp of 1 / U, and the third is
+// Markstein's correcting step from there: y = RN(1 / U) unless U's
+// significand is all ones (1 / U then sits just above a rounding midpoint the
+// step cannot see).  div_by_recip: with y = RN(1 / U), q0 = RN(u y) is off
+// u / U by less than 1.5 ulp (|u y - u / U| = u |y - 1 / U| <= u ulp(y) / 2,
+// under 1 ulp of the quotient; the rounding adds half), the residual r = u - U q0 comes
+// out of one FMA, and RN(q0 + r y) is the quotient.  Markstein's theorem
+// asks for a faithful q0 (within 1 ulp); that the sequence as written gives
+// RN(u / U) for the q0 it really gets rests on the check in
+// tests/check_share_div.c over the seeds the hardware reciprocal can
+// return, not on an argument here.  (With two Newton steps the sequence is
+// the one the compiler emits for `/` itself.)
+//
+// Both theorems are statements about significands; they carry over to the
+// operands as long as no intermediate leaves the normal range.  share_window
+// keeps U and every non-zero u in [2^-256, 2^256), sign clear (so exponents
+// differ by at most 511).  With eU, eu the exponents of U and u:
+//   y is in (2^-256, 2^256];  U y is in (1/2, 2), so 1 - U y is 0 or a
+//   multiple of ulp(U) ulp(y) = 2^(eU-52) 2^(-eU-1-52) >= 2^-106, whatever eU;
+//   q0 and q are in (2^-512, 2^512), exponent eq >= eu - eU - 1;
+//   r is 0 or a multiple of ulp(U) ulp(q0) = 2^(eU-52) 2^(eq-52) >= 2^(eu-105)
+//   >= 2^-361, and |r| <= 2 ulp(q0) U < 2^(eu-50);  r y is about 2^(eq-53).
+// Nothing underflows, overflows or is subnormal, and a zero residual is
+// exact.  u = +0 gives q0 = r = q = +0 = u / U for any such U; -0 (whose
+// quotient is -0), negative, subnormal, infinite and NaN operands are
+// outside.  The all-ones exception is excluded by its low word: any U whose
+// low 32 bits are all ones declines (1 divisor in 2^32).  Outside the window
+// the caller divides.
+//
+// The test is per month, on U and the PREG registers together: the largest
+// high word (u >= 0 compares as its bits; a set sign bit or Inf / NaN
+// exceeds every accepted word) and the smallest binary exponent
+// (v_frexp_exp_i32_f64: 0 for +-0, so zeros pass; true exponent + 1 for
+// normal and subnormal values).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t hi32(double x) { return (uint32_t)__double2hiint(x); }
+__device__ __forceinline__ uint32_t lo32(double x) { return (uint32_t)__double2loint(x); }
+
+__device__ __forceinline__ bool share_window(double U, const double (&u)[PREG]) {
+    uint32_t hmax = hi32(U);
+    int emin = 0;
+#pragma unroll
+    for (int p = 0; p < PREG; p++) {
+        const uint32_t h = hi32(u[p]);
+        const int e = __builtin_amdgcn_frexp_exp(u[p]);
+        hmax = h > hmax ? h : hmax;
+        emin = e < emin ? e : emin;
+    }
+    return U >= 0x1p-256 && hmax < 0x4FF00000u && emin >= -255 && lo32(U) != 0xFFFFFFFFu;
+}
+
+// RN(1 / U) for U inside share_window
+__device__ __forceinline__ double recip_rn(double U) {
+    double y = __builtin_amdgcn_rcp(U);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double e = __builtin_fma(-U, y, 1.0);
+        y = __builtin_fma(y, e, y);
+    }
+    return y;
+}
+
+// RN(u / U) from y = recip_rn(U), u and U inside share_window
+__device__ __forceinline__ double div_by_recip(double u, double U, double y) {
+    const double q0 = u * y;
+    const double r = __builtin_fma(-U, q0, u);
+    return __builtin_fma(r, y, q0);
+}
+
+// fr[p] = u[p] / U for the periods p < P of a month (U > 0): the shared
+// reciprocal inside the window, the division outside.  Registers at and
+// above P hold +0 in every caller (their shares are never read).
+__device__ __forceinline__ bool month_shares(const double (&u)[PREG], double U, int P, double (&fr)[PREG]) {
+    const bool fast = share_window(U, u);
+    if (__builtin_expect(fast, 1)) {
+        const double y = recip_rn(U);
+#pragma unroll
+        for (int p = 0; p < PREG; p++) fr[p] = div_by_recip(u[p], U, y);
+    } else {
+#pragma unroll
+        for (int p = 0; p < PREG; p++) fr[p] = p < P ? u[p] / U : 0.0;
+    }
+    return fast;
+}
+
+// Which year-lane search / evaluation instantiations take month_shares in
+// their NEM bills: all but the two-agents-per-wave net-billing one without
+// demand charges (k_size_w / k_eval_w<32, false, true, false>).  That kernel
+// sits at its 168-VGPR cap, month_shares cost it one more spill slot
+// (388 -> 392 B) and 0.7 % of its time on the net-billing workload, whose
+// evaluations are dominated by the hourly bill; it keeps the quotients.
+template <int LPA, bool DC, bool NET, bool PK>
+__host__ __device__ constexpr bool recip_shares() { return !(LPA == 32 && !DC && NET && !PK); }
+
+// ---------------------------------------------------------------------------
 // numpy pairwise summation (loops_utils.h.src), chunked by the 8192-element
 // reduction buffer; identical association order => bit-identical to np.sum.
 // ---------------------------------------------------------------------------
@@ -1767,6 +1868,9 @@ __device__ __forceinline__ double yl_bill_mo0(const dgen_tariff& t, const YLds& 
 // Same bill with the per-period credits and billed kWh in registers (P <= 4,
 // the common case): loops run to the compile-time bound under the uniform
 // guard p < P, so the order of every sum is the LDS version's.
+// RECIP: the tiered months' shares by month_shares (false: the plain
+// quotients, for the instantiation recip_shares() names).
+template <bool RECIP = true>
 __device__ __forceinline__ double yl_bill_mo0_reg(const dgen_tariff& t, const YLds& S, double gscale,
                                                   double yearend) {
     const int P = t.P, T = t.T, half = S.half;
@@ -1808,8 +1912,12 @@ __device__ __forceinline__ double yl_bill_mo0_reg(const dgen_tariff& t, const YL
                 // each period's share of the month, once per month (the same
                 // quotient the tier loop used to recompute per tier)
                 double fr[PREG];
+                if constexpr (RECIP) {
+                    month_shares(u, U, P, fr);
+                } else {
 #pragma unroll
-                for (int p = 0; p < PREG; p++) fr[p] = p < P ? u[p] / U : 0.0;
+                    for (int p = 0; p < PREG; p++) fr[p] = p < P ? u[p] / U : 0.0;
+                }
                 const double scale = tier_scale(t, m, S.pk);
                 double prev = 0.0;
                 for (int k = 0; k < T; k++) {
@@ -1837,10 +1945,11 @@ __device__ __forceinline__ double yl_bill_mo0_reg(const dgen_tariff& t, const YL
     return total;
 }
 
+template <bool RECIP = true>
 __device__ __forceinline__ double yl_bill_nem(const dgen_tariff& t, const YLds& S, double gscale,
                                               double yearend) {
     if (t.mo != 0) return yl_bill_bins_ext(t, S, gscale);                 // options 1 and 4
-    return (t.P <= PREG) ? yl_bill_mo0_reg(t, S, gscale, yearend) : yl_bill_mo0(t, S, gscale, yearend);
+    return (t.P <= PREG) ? yl_bill_mo0_reg<RECIP>(t, S, gscale, yearend) : yl_bill_mo0(t, S, gscale, yearend);
 }
 
 // The no-system NEM bill (gscale 0): every month nets its load (>= 0), so no
@@ -1848,10 +1957,10 @@ __device__ __forceinline__ double yl_bill_nem(const dgen_tariff& t, const YLds& 
 // the segment bills month m with yl_bill_mo0_reg's arithmetic (credit 0),
 // then the months are added in order, the serial loop's sum.  A negative
 // bin (months then depend on each other) or P > PREG takes the serial bill.
-template <int LPA>
+template <int LPA, bool RECIP = true>
 __device__ __forceinline__ double yl_bill_nem_nosys(const dgen_tariff& t, const YLds& S, double yearend,
                                                     const Seg<LPA>& g) {
-    if (t.mo != 0 || t.P > PREG) return yl_bill_nem(t, S, 0.0, yearend);
+    if (t.mo != 0 || t.P > PREG) return yl_bill_nem<RECIP>(t, S, 0.0, yearend);
     const int P = t.P, T = t.T, half = S.half;
     const int m = g.sl < 12 ? g.sl : 11;
     double b0[PREG], u[PREG], credit[PREG];
@@ -1872,7 +1981,7 @@ __device__ __forceinline__ double yl_bill_nem_nosys(const dgen_tariff& t, const 
             neg = neg || !pos;
         }
     }
-    if (g.first(neg) >= 0) return yl_bill_nem(t, S, 0.0, yearend);
+    if (g.first(neg) >= 0) return yl_bill_nem<RECIP>(t, S, 0.0, yearend);
     double U = 0.0;
 #pragma unroll
     for (int p = 0; p < PREG; p++)
@@ -1885,8 +1994,12 @@ __device__ __forceinline__ double yl_bill_nem_nosys(const dgen_tariff& t, const 
                 if (p < P) charge += u[p] * b0[p];
         } else {
             double fr[PREG];
+            if constexpr (RECIP) {
+                month_shares(u, U, P, fr);
+            } else {
 #pragma unroll
-            for (int p = 0; p < PREG; p++) fr[p] = p < P ? u[p] / U : 0.0;
+                for (int p = 0; p < PREG; p++) fr[p] = p < P ? u[p] / U : 0.0;
+            }
             const double scale = tier_scale(t, m, S.pk);
             double prev = 0.0;
             for (int k = 0; k < T; k++) {
@@ -1964,8 +2077,7 @@ __device__ __forceinline__ double reg_month_charge(const dgen_tariff& t, int m, 
         return charge;
     }
     double fr[PREG];
-#pragma unroll
-    for (int p = 0; p < PREG; p++) fr[p] = p < P ? u[p] / U : 0.0;
+    month_shares(u, U, P, fr);
     const double scale = tier_scale(t, m, pk);
     double prev = 0.0;
     for (int k = 0; k < T; k++) {
@@ -3678,7 +3790,7 @@ __device__ __forceinline__ void yl_set_tariff(YCtx<LPA>& c, int tix) {
         PH_T0(tn);
         wave_lds_sync();
         yl_build_bins(t, c.lslots, c.gslots, c.load_scale, c.S, c.g);
-        c.wo1 = yl_bill_nem_nosys(t, c.S, c.yearend, c.g);
+        c.wo1 = yl_bill_nem_nosys<LPA, recip_shares<LPA, DC, NET, PK>()>(t, c.S, c.yearend, c.g);
         PH_ADD_KS(12, tn, c.g.sl == 0);        // NEM set_tariff (bins + no-system bill)
     } else if constexpr (NET) {
         // net billing: the no-system bill from the load bins
@@ -3729,7 +3841,7 @@ __device__ __forceinline__ double yl_objective(YCtx<LPA>& c, double kw) {
     }
     if (!net_hourly(t)) {
         PH_T0(tn);
-        wb = yl_bill_nem(t, c.S, c.s_y * kws, c.yearend);
+        wb = yl_bill_nem<recip_shares<LPA, DC, NET, PK>()>(t, c.S, c.s_y * kws, c.yearend);
         PH_ADD_KS(13, tn, c.g.sl == 0);        // NEM evaluation bill
     } else if constexpr (NET) {
         if (c.nb_pending) {
@@ -4711,6 +4823,27 @@ __global__ void k_brent_selftest(const double* lo, const double* hi, const doubl
         lo[i], hi[i], xatol[i], &nf, &xl);
     xopt[i] = xo;
     nfev[i] = nf;
+}
+
+// ---------------------------------------------------------------------------
+// Share self-test kernel: the bills' month_shares on one month per thread
+// (PREG billed-kWh registers and their divisor) beside the plain quotients;
+// fast is the branch month_shares took
+// ---------------------------------------------------------------------------
+__global__ void k_share_selftest(const double* __restrict__ u, const double* __restrict__ U, int64_t n,
+                                 double* __restrict__ q, double* __restrict__ ref, int32_t* __restrict__ fast) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double uu[PREG], fr[PREG];
+#pragma unroll
+    for (int p = 0; p < PREG; p++) uu[p] = u[i * PREG + p];
+    const bool f = month_shares(uu, U[i], PREG, fr);
+#pragma unroll
+    for (int p = 0; p < PREG; p++) {
+        q[i * PREG + p] = fr[p];
+        ref[i * PREG + p] = uu[p] / U[i];
+    }
+    fast[i] = f ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -11231,6 +11364,20 @@ int32_t dgen_brent_selftest(dgen_ctx* c, const double* lo, const double* hi, con
     HIP_TRY(hipSetDevice(c->device));
     hipLaunchKernelGGL(k_brent_selftest, dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
                        (hipStream_t)stream, lo, hi, xatol, c2, x0, c1, n, xs, maxn, xopt, nfev);
+    HIP_TRY(hipGetLastError());
+    return DGEN_OK;
+}
+
+int32_t dgen_share_selftest(dgen_ctx* c, const double* u, const double* U, int64_t n, double* q,
+                            double* ref, int32_t* fast, void* stream) {
+    if (!c || !u || !U || !q || !ref || !fast) {
+        set_err("dgen_share_selftest: bad argument");
+        return DGEN_E_ARG;
+    }
+    if (n <= 0) return DGEN_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_share_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, u, U, n, q, ref, fast);
     HIP_TRY(hipGetLastError());
     return DGEN_OK;
 }

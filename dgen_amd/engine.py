@@ -1026,6 +1026,31 @@ class Engine:
         torch.cuda.synchronize(self.dev)
         return xs.cpu().numpy(), xo.cpu().numpy(), nf.cpu().numpy()
 
+    def share_selftest(self, u, U):
+        """The tiered bills' share helper on months (u[i, 0..3], U[i]): its four
+        shares, the plain device quotients and whether the month took the
+        reciprocal path.  A 1-D u is one register per month, the others +0."""
+        torch = _torch()
+        u = np.asarray(u, dtype=np.float64)
+        one = u.ndim == 1
+        if one:
+            u = np.concatenate([u[:, None], np.zeros((u.size, 3))], axis=1)
+        if u.ndim != 2 or u.shape[1] != 4:
+            raise ValueError("u is [n] or [n, 4]")
+        tu = self._to_dev(np.ascontiguousarray(u), torch.float64)
+        tU = self._to_dev(np.asarray(U, dtype=np.float64), torch.float64)
+        n = u.shape[0]
+        if tU.numel() != n:
+            raise ValueError("u and U differ in length")
+        q = torch.zeros((n, 4), dtype=torch.float64, device=self.dev)
+        ref = torch.zeros((n, 4), dtype=torch.float64, device=self.dev)
+        fast = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.dgen_share_selftest(self.ctx, _ptr(tu), _ptr(tU), n, _ptr(q), _ptr(ref),
+                                                _ptr(fast), self.stream_handle()), "dgen_share_selftest")
+        torch.cuda.synchronize(self.dev)
+        q, ref = q.cpu().numpy(), ref.cpu().numpy()
+        return (q[:, 0], ref[:, 0], fast.cpu().numpy()) if one else (q, ref, fast.cpu().numpy())
+
 
 def hourly_plane(t):
     """A hourly output plane in its device tiles [NH/4][n][4] -> the logical

@@ -324,6 +324,15 @@ int32_t dgen_brent_selftest(dgen_ctx* ctx, const double* lo, const double* hi,
                             const double* c1, int64_t n, double* xs, int32_t maxn,
                             double* xopt, int32_t* nfev, void* stream);
 
+/* Test entry: the tiered bills' period shares u[p] / U of a month as the
+ * year-lane kernels form them (one corrected reciprocal of U inside the
+ * helper's operand window, the divisions outside).  Per month i: u[4 i .. 4 i + 3]
+ * the four billed-kWh registers, U[i] their divisor; q the helper's shares,
+ * ref the plain device quotients ([n][4] each), fast[i] 1 where the month
+ * was inside the window.                                                     */
+int32_t dgen_share_selftest(dgen_ctx* ctx, const double* u, const double* U, int64_t n,
+                            double* q, double* ref, int32_t* fast, void* stream);
+
 /* Deterministic weighted segmented sums over contiguous agent ranges, for the
  * per-(state, sector) totals and per-state 8760-h net sums that feed diffusion
  * (replaces size_chunk's running net_sum, ff:1173-1188, and the per-state
