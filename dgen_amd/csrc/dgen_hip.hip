@@ -1382,10 +1382,12 @@ k_hourly_batt(dgen_tables T, dgen_agents A, dgen_outputs O, dgen_cfg cfg, int64_
                 if constexpr (ROLL) {
                     // this hour's plan over hours h .. h + 23, from the energy
                     // stored now; only an hour that can discharge needs one
-                    // (elsewhere the dispatch is the same for any target)
+                    // (elsewhere the dispatch is the same for any target); under
+                    // the month floor every deficit hour plans, stored energy or
+                    // not, so that rounding dust of it cannot decide the floor
                     const double av = LOSS ? fmax((soc - cfg.batt_min_soc) * bank, 0.0) * cfg.batt_conv_eff
                                            : fmax((soc - cfg.batt_min_soc) * bank * cfg.batt_eta_out, 0.0);
-                    const bool need = has_batt && nn > 0.0 && av > 0.0;
+                    const bool need = has_batt && nn > 0.0 && (av > 0.0 || cfg.batt_month_floor);
                     target = 0.0;
                     if (__ballot(need)) {
                         double dv[24];

@@ -562,7 +562,13 @@ static double day_target(const double* load, const double* pv, int h0, double po
  *       hours (bdh:86-87 read literally: batt_look_ahead_hours = 24,
  *       batt_dispatch_update_frequency_hours = 1).  A plan only matters in an
  *       hour that can discharge (net load > 0, energy stored > 0), so the
- *       hourly rule forms it only there; the result is the same.            */
+ *       hourly rule forms it only there; the result is the same.  Under the
+ *       month floor a plan also raises the floor, so there the rule plans in
+ *       every deficit hour, stored energy or not, as the daily plan does at a
+ *       day's first hour: with nothing stored the target is the window's
+ *       largest deficit, which is also the limit as the stored energy goes to
+ *       0.  (Gated on energy stored > 0, rounding dust left by a clamped
+ *       discharge decided whether the floor jumped there.)                   */
 /* Li-ion loss model (cfg->batt_loss_model = 1): converters of efficiency
  * batt_conv_eff each way, and the cells' I^2 R at the bank's open-circuit
  * voltage.  With s cells in series and p strings (battery_model_sizing) the
@@ -614,8 +620,9 @@ void orc_batt_dispatch(const double* load, const double* pv, double bank_kwh, do
                 double e_av = (soc - cfg->batt_min_soc) * bank_kwh;
                 if (e_av < 0.0) e_av = 0.0;
                 if (!hourly) target = day_target(load, pv, h, power_kw, e_av * eta);
-                else target = (n > 0.0 && e_av > 0.0) ? day_target(load, pv, h, power_kw, e_av * eta) : 0.0;
-                if (mfl && (!hourly || (n > 0.0 && e_av > 0.0))) {
+                const int plan = n > 0.0 && (e_av > 0.0 || mfl);
+                if (hourly) target = plan ? day_target(load, pv, h, power_kw, e_av * eta) : 0.0;
+                if (mfl && (!hourly || plan)) {
                     if (target < floor_t) target = floor_t;
                     else floor_t = target;
                 }
@@ -670,8 +677,9 @@ void orc_batt_dispatch(const double* load, const double* pv, double bank_kwh, do
             double avail = (soc - cfg->batt_min_soc) * bank_kwh * cfg->batt_eta_out;
             if (avail < 0.0) avail = 0.0;
             if (hourly) {
-                target = (n > 0.0 && avail > 0.0) ? day_target(load, pv, h, power_kw, avail) : 0.0;
-                if (mfl && n > 0.0 && avail > 0.0) {
+                const int plan = n > 0.0 && (avail > 0.0 || mfl);
+                target = plan ? day_target(load, pv, h, power_kw, avail) : 0.0;
+                if (mfl && plan) {
                     if (target < floor_t) target = floor_t;
                     else floor_t = target;
                 }
